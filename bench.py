@@ -22,8 +22,15 @@ Other BASELINE.json configs (``--config``; per-GPU shapes are the 8-GPU configs 
 * ``tron``:  Poisson + L2, TRON (one STEP = one outer trust-region iteration incl. its Hessian-vector CG passes),
   62.5M rows/GPU x 1M features (config "Poisson regression TRON, 500M rows, 8 GPUs").
 
-Usage: python bench.py [--gpus N --steps K --warmup W] [--config lbfgs|owlqn|tron]; for N > 1 either launch with
-torch.distributed.run (one rank per GPU) or let bench.py start that launcher itself as a child process.
+Usage: python bench.py [--gpus N --steps K --warmup W] [--config lbfgs|owlqn|tron] [--full] [--dump-outputs DIR];
+for N > 1 either launch with torch.distributed.run (one rank per GPU) or let bench.py start that launcher itself
+as a child process.
+
+A plain run does only what the headline figure needs: data generation, warm-up, the timed steps, one JSON line.
+``--full`` adds the other measurements to the same record (``--game`` / ``--configs-extra``: the GAME metric and
+BASELINE.json configs 3 and 4 at fp64 and bf16). ``--dump-outputs DIR`` writes what the last timed step returned
+(the optimizer state: coefficients, gradient, loss) as ``DIR/<name>.npy``; the inputs are a function of the
+arguments alone (``--seed``), so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -73,16 +80,25 @@ def main():
                     help="after the timed GLM steps, also time BASELINE.json's GAME metric (coordinate-descent sweeps "
                          "of config 5 with power-law entity sizes, bench_game.py --config game5pl; entity-sharded over "
                          "the ranks when N > 1) with bf16 and with fp64 fixed-effect features, reported as extra "
-                         "keys; auto = on for the lbfgs config")
+                         "keys; auto = on for the lbfgs config under --full")
     ap.add_argument("--configs-extra", default="auto", choices=["auto", "on", "off"],
                     help="after the headline (and GAME), also time BASELINE.json configs 3 (OWL-QN, 10M features) and "
                          "4 (Poisson TRON) at fp64 feature storage (the reference's precision; rows reduced to what "
                          "fits in HBM, stated in the keys) and bf16, reported as extra keys; auto = on for the lbfgs "
-                         "config at its full size on one rank")
+                         "config at its full size on one rank under --full")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline that --game auto / --configs-extra auto select "
+                         "(off by default: a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the state the last timed step returned (coefficients, "
+                         "gradient, loss) as DIR/<name>.npy in float64; arrays above DUMP_MAX_ELEMS entries are "
+                         "written as a fixed seeded sample of their entries")
     ap.add_argument("--rehearsal", action="store_true",
                     help="allow more ranks than physical devices (several ranks per GPU, or CPU ranks); the record "
                          "then says rehearsal: true, and n_gpus counts devices, not ranks")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     cfg = CONFIGS[args.config]
     if args.rows_per_gpu is None:
         args.rows_per_gpu = cfg["rows_per_gpu"]
@@ -113,7 +129,7 @@ def main():
     # the GAME metric first, in the process state a GAME user has (no 120 GB of another benchmark's buffers just
     # returned to the driver: after the headline's release the GAME build measured 2.1-5.2 s box to box, 2.0-2.2 s
     # in a fresh process); the headline's timed steps come after its own untimed data generation and warm-up
-    if args.game == "on" or (args.game == "auto" and args.config == "lbfgs"):
+    if args.game == "on" or (args.game == "auto" and args.full and args.config == "lbfgs"):
         game = game_extra(dev, rank, world)
         gc.collect()
         torch.cuda.empty_cache()
@@ -124,12 +140,14 @@ def main():
     sharded = args.optimizer_state == "feature-sharded"
     value = total_rows * args.steps / elapsed
     del res
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, st)
     gc.collect()
     torch.cuda.empty_cache()
     cfgx = None
     full_size = args.rows_per_gpu == cfg["rows_per_gpu"] and args.features == cfg["features"]
-    if args.configs_extra == "on" or (args.configs_extra == "auto" and args.config == "lbfgs" and world == 1
-                                      and full_size):
+    if args.configs_extra == "on" or (args.configs_extra == "auto" and args.full and args.config == "lbfgs"
+                                      and world == 1 and full_size):
         cfgx = configs_extra(dev, rank, world, args)
     if rank == 0:
         log(f"final f={st.loss:.6e} |g|={gnorm:.3e} evals/step={passes / args.steps:.2f} "
@@ -173,6 +191,29 @@ def main():
         if cfgx is not None:
             out.update(cfgx)
         print(json.dumps(out), flush=True)
+
+
+# --dump-outputs: entries written per array (float64: 24 MB each, two vectors + the loss stay under 64 MB)
+DUMP_MAX_ELEMS = 3_000_000
+DUMP_SAMPLE_SEED = 20261019
+
+
+def dump_outputs(directory: str, state) -> None:
+    """Write the optimizer state the last timed step returned -- what a caller of ``opt.step`` receives -- as
+    ``coefficients.npy``, ``gradient.npy`` and ``loss.npy`` (float64; rank 0's state, its feature slice under
+    ``--optimizer-state feature-sharded``). A vector longer than ``DUMP_MAX_ELEMS`` is written as its entries at a
+    fixed seeded choice of sorted positions (a function of its length alone)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {"coefficients": state.coefficients, "gradient": state.gradient}
+    for name, t in arrays.items():
+        a = t.detach().to("cpu").numpy().astype(np.float64, copy=False).reshape(-1)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a[idx]
+        np.save(os.path.join(directory, f"{name}.npy"), np.ascontiguousarray(a))
+    np.save(os.path.join(directory, "loss.npy"), np.asarray([float(state.loss)], dtype=np.float64))
+    log(f"outputs of the last timed step written to {directory}")
 
 
 # feature-storage bytes per non-zero of a tiled shard (forward + transpose copies, measured: bf16 115.5 GiB for

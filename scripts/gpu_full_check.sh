@@ -1,11 +1,13 @@
 #!/bin/bash
-# Full check (output dir = $1): full GPU test suite, smoke, headline bench (+ game5pl bf16 / fp64 keys).
+# Full check (output dir = bench_results/$1): full GPU test suite, smoke, the whole benchmark record
+# (bench.py --full: headline + game5pl bf16 / fp64 keys + configs 3 / 4).
 set -o pipefail
-mkdir -p gpurun_out/${1:-r4full}
+out=bench_results/${1:-full_check}
+mkdir -p $out
 export TMPDIR=/tmp
-timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > gpurun_out/${1:-r4full}/pytest_gpu.log 2>&1 || { echo "pytest failed"; tail -40 gpurun_out/${1:-r4full}/pytest_gpu.log; exit 1; }
-tail -2 gpurun_out/${1:-r4full}/pytest_gpu.log
-timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > gpurun_out/${1:-r4full}/smoke.log 2>&1 || { echo "smoke failed"; tail -20 gpurun_out/${1:-r4full}/smoke.log; exit 1; }
-tail -1 gpurun_out/${1:-r4full}/smoke.log
-timeout -k 10 600 python -u bench.py --steps 20 --warmup 5 > gpurun_out/${1:-r4full}/bench.json 2> gpurun_out/${1:-r4full}/bench.log || { echo "bench failed"; tail -30 gpurun_out/${1:-r4full}/bench.log; exit 1; }
-cat gpurun_out/${1:-r4full}/bench.json
+timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > $out/pytest_gpu.log 2>&1 || { echo "pytest failed"; tail -40 $out/pytest_gpu.log; exit 1; }
+tail -2 $out/pytest_gpu.log
+timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $out/smoke.log 2>&1 || { echo "smoke failed"; tail -20 $out/smoke.log; exit 1; }
+tail -1 $out/smoke.log
+timeout -k 10 600 python -u bench.py --full --steps 20 --warmup 5 > $out/bench.json 2> $out/bench.log || { echo "bench failed"; tail -30 $out/bench.log; exit 1; }
+cat $out/bench.json

@@ -33,6 +33,26 @@ def test_bench_contract_tiny():
     assert rec["config"]["parallelism"] == "dp1"
 
 
+def test_bench_plain_run_is_headline_only_and_dumps_outputs(tmp_path):
+    """A plain run reports the headline alone (the GAME / configs 3-4 keys belong to --full) and --dump-outputs
+    writes the last timed step's state; the same arguments give the same arrays, and --steps sets how many timed
+    steps produced them."""
+    import numpy as np
+    tiny = ["--warmup", "1", "--rows-per-gpu", "100000", "--features", "5000"]
+    recs = {}
+    for tag, steps in (("a", "2"), ("b", "2"), ("c", "3")):
+        recs[tag] = _run(["bench.py", "--steps", steps, "--dump-outputs", str(tmp_path / tag), *tiny])
+    assert not [k for k in recs["a"] if k.startswith(("game5pl", "owlqn10m", "tron_poisson"))]
+    assert recs["a"]["steps"] == 2 and recs["c"]["steps"] == 3
+    out = {t: {n: np.load(tmp_path / t / f"{n}.npy") for n in ("coefficients", "gradient", "loss")} for t in recs}
+    for n, shape in (("coefficients", (5000,)), ("gradient", (5000,)), ("loss", (1,))):
+        assert out["a"][n].dtype == np.float64 and out["a"][n].shape == shape
+        assert np.isfinite(out["a"][n]).all()
+        assert np.array_equal(out["a"][n], out["b"][n]), n
+    assert out["c"]["loss"][0] < out["a"]["loss"][0]        # a third timed step went further down
+    assert np.abs(out["a"]["coefficients"]).max() > 0
+
+
 def test_bench_game_contract_tiny():
     rec = _run(["bench_game.py", "--steps", "1", "--warmup", "1", "--entities-per-gpu", "2000",
                 "--rows-per-entity", "10", "--re-dim", "50", "--re-nnz", "5", "--fe-dim", "5000", "--fe-nnz", "10"])

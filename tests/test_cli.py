@@ -161,7 +161,7 @@ def test_libsvm_to_avro_roundtrip(tmp_path):
     """dev-scripts/libsvm_text_to_trainingexample_avro.py analogue: LibSVM heart -> Avro -> same matrix."""
     from photon_ml_amd.io.data_reader import AvroDataReader, read_libsvm
     from photon_ml_amd.tools.libsvm_to_avro import convert
-    src = "/root/reference/photon-client/src/integTest/resources/DriverIntegTest/input/heart.txt"
+    src = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "DriverIntegTest", "input", "heart.txt")
     n = convert(src, str(tmp_path / "heart"), records_per_file=100, binarize=True)
     assert n == 250 and len(os.listdir(tmp_path / "heart")) == 3
     ld_avro, im = AvroDataReader().read_labeled(str(tmp_path / "heart"))

@@ -3,7 +3,8 @@
 Reference: ``photon-client/src/integTest/scala/com/linkedin/photon/ml/DriverTest.scala`` (stages, number of
 models, best model only with validation data, LibSVM input, invalid parameter combinations),
 ``photon-diagnostics/src/test/.../{hl,independence,featureimportance}`` and the Evaluation metric definitions.
-Data: the reference's own heart.avro / heart.txt fixtures.
+Data: the reference's own heart.avro / heart.txt fixtures, stored under ``tests/fixtures`` and ``tests/golden``
+(a9a / a9a.t gzip-compressed there and unpacked into the test's scratch directory).
 """
 import os
 
@@ -16,13 +17,15 @@ from photon_ml_amd.diagnostics import evaluation as ev
 from photon_ml_amd.diagnostics.diagnostics import hosmer_lemeshow, kendall_tau
 from photon_ml_amd.io.index_map import DefaultIndexMap
 
-REF = "/root/reference/photon-client/src/integTest/resources/DriverIntegTest/input"
+HERE = os.path.dirname(os.path.abspath(__file__))
+FIX = os.path.join(HERE, "fixtures")
+REF = os.path.join(HERE, "golden", "DriverIntegTest", "input")
 HEART_FEATURES = 14
 HEART_ROWS = 250
 
 
 def run(tmp_path, *extra, out="out"):
-    args = ["--training-data-directory", f"{REF}/heart.avro", "--output-directory", str(tmp_path / out),
+    args = ["--training-data-directory", f"{FIX}/heart.avro", "--output-directory", str(tmp_path / out),
             "--task", "LOGISTIC_REGRESSION", "--num-iterations", "50", "--device", "cpu", *extra]
     return drv.Driver(drv.build_parser().parse_args(args)).run()
 
@@ -39,7 +42,7 @@ def test_minimal_run(tmp_path):
 
 
 def test_validation_selects_best_and_diagnoses(tmp_path):
-    d = run(tmp_path, "--validating-data-directory", f"{REF}/heart_validation.avro",
+    d = run(tmp_path, "--validating-data-directory", f"{FIX}/heart_validation.avro",
             "--regularization-weights", "0.1,1,10,100", "--diagnostic-mode", "VALIDATE",
             "--summarization-output-dir", str(tmp_path / "summary"), "--normalization-type", "STANDARDIZATION")
     assert d.stage == drv.DriverStage.DIAGNOSED
@@ -167,7 +170,13 @@ def test_driver_linear_regression_diagnostic_matrix(tmp_path, reg, opt, lams):
 def test_a9a_logistic_libsvm_quality(tmp_path):
     """a9a (the reference's LOGISTIC fixture: 32,561 rows, 123 features + intercept = 124) as LibSVM: L2
     logistic regression validated on a9a.t reaches the usual a9a quality (AUC ~0.90)."""
-    args = ["--training-data-directory", f"{REF}/a9a", "--validating-data-directory", f"{REF}/a9a.t",
+    import gzip
+    import shutil
+    for name in ("a9a", "a9a.t"):
+        with gzip.open(f"{REF}/{name}.gz", "rb") as src, open(tmp_path / name, "wb") as dst:
+            shutil.copyfileobj(src, dst)
+    args = ["--training-data-directory", str(tmp_path / "a9a"), "--validating-data-directory",
+            str(tmp_path / "a9a.t"),
             "--output-directory", str(tmp_path / "o"), "--task", "LOGISTIC_REGRESSION", "--input-file-format",
             "LIBSVM", "--feature-dimension", "123", "--regularization-weights", "1", "--num-iterations", "100",
             "--device", "cpu"]

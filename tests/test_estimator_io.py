@@ -24,7 +24,8 @@ from photon_ml_amd.stat.summary import BasicStatisticalSummary
 
 from test_optimizers import trivial_data
 
-REF = "/root/reference/photon-client/src/integTest/resources"
+HERE = os.path.dirname(os.path.abspath(__file__))
+REF = os.path.join(HERE, "golden")       # the reference's integration-test resources that these tests read
 
 
 @pytest.mark.parametrize("ntype", list(NormalizationType))
@@ -121,7 +122,7 @@ def test_game_model_save_load_roundtrip(tmp_path):
 
 def test_avro_data_reader_heart():
     from photon_ml_amd.io.data_reader import AvroDataReader, FeatureShardConfiguration
-    data, maps = AvroDataReader().read(f"{REF}/DriverIntegTest/input/heart.avro",
+    data, maps = AvroDataReader().read(os.path.join(HERE, "fixtures", "heart.avro"),
                                        {"s": FeatureShardConfiguration(["features"], True)})
     assert data.n_rows == 250 and data.shards["s"].shape == (250, 14)
     assert maps["s"].intercept_index == 13

@@ -4,7 +4,7 @@ Reference expectations: ``photon-api/src/test/scala/com/linkedin/photon/ml/index
 (exact name -> index values of the heart stores, 2 partitions, with and without intercept); the GAME
 integration-test stores ``GameIntegTest/input/feature-indexes/paldb-partition-shard{1,2,3}-0.dat`` and the
 duplicate-feature Avro input of ``AvroDataReaderIntegTest.scala:85``. The heart stores and the duplicate-feature
-Avro file are copied into ``tests/fixtures``; the (larger) GAME stores are read from the reference tree.
+Avro file are copied into ``tests/fixtures``, the (larger) GAME stores and feature lists into ``tests/golden``.
 """
 import os
 
@@ -16,8 +16,14 @@ from photon_ml_amd.io.index_map import open_index_map
 from photon_ml_amd.io.paldb import PalDBIndexMap, partition_of, read_store
 
 FIX = os.path.join(os.path.dirname(__file__), "fixtures")
-GAME = "/root/reference/photon-client/src/integTest/resources/GameIntegTest/input"
+GAME = os.path.join(os.path.dirname(__file__), "golden", "GameIntegTest", "input")
 DELIM = "\u0001"
+
+
+def game_store(shard):
+    """A GAME store as a test parameter whose id does not depend on where the repository is checked out."""
+    rel = f"golden/GameIntegTest/input/feature-indexes/paldb-partition-{shard}-0.dat"
+    return pytest.param(os.path.join(GAME, "feature-indexes", f"paldb-partition-{shard}-0.dat"), id=rel)
 
 
 def key(name, term=""):
@@ -59,7 +65,6 @@ def test_partitioning_is_spark_hash_partitioner():
             assert names and all(partition_of(k, 2) == p for k in names)
 
 
-@pytest.mark.skipif(not os.path.isdir(GAME), reason="reference GAME integration-test inputs not present")
 def test_game_integration_stores():
     maps = {s: PalDBIndexMap(os.path.join(GAME, "feature-indexes"), s, 1) for s in ("shard1", "shard2", "shard3")}
     for m in maps.values():
@@ -98,8 +103,7 @@ def test_legacy_driver_trains_with_reference_paldb_index(tmp_path):
     """DriverIntegTest with an off-heap index map: the heart PalDB stores (with intercept) drive the feature
     indexing of the heart Avro input; the learned model is laid out in the store's index order."""
     from photon_ml_amd.cli import driver as drv
-    ref = "/root/reference/photon-client/src/integTest/resources/DriverIntegTest/input/heart.avro"
-    train = ref if os.path.exists(ref) else os.path.join(FIX, "heart.avro")
+    train = os.path.join(FIX, "heart.avro")
     args = ["--training-data-directory", train, "--output-directory", str(tmp_path / "o"), "--task",
             "LOGISTIC_REGRESSION", "--num-iterations", "30", "--device", "cpu", "--offheap-indexmap-dir",
             os.path.join(FIX, "paldb_heart_icpt"), "--offheap-indexmap-num-partitions", "2"]
@@ -128,13 +132,10 @@ def _rebuild(path, out):
 @pytest.mark.parametrize("path", [os.path.join(FIX, "paldb_heart", "paldb-partition-global-0.dat"),
                                   os.path.join(FIX, "paldb_heart", "paldb-partition-global-1.dat"),
                                   os.path.join(FIX, "paldb_heart_icpt", "paldb-partition-global-0.dat"),
-                                  os.path.join(GAME, "feature-indexes", "paldb-partition-shard1-0.dat"),
-                                  os.path.join(GAME, "feature-indexes", "paldb-partition-shard3-0.dat")])
+                                  game_store("shard1"), game_store("shard3")])
 def test_writer_reproduces_reference_stores_bytewise(path, tmp_path):
     """Rewriting a reference store's contents (keys inserted by index, its timestamp) gives the SAME bytes: slot
     hash (murmur3, seed 42), slot counts, slot widths, int / string serialisation, data layout."""
-    if not os.path.exists(path):
-        pytest.skip("reference store not present")
     ref, out = _rebuild(path, str(tmp_path / "s.dat"))
     assert out == ref
 
@@ -191,17 +192,13 @@ STORES = [os.path.join(FIX, "paldb_heart", "paldb-partition-global-0.dat"),
           os.path.join(FIX, "paldb_heart", "paldb-partition-global-1.dat"),
           os.path.join(FIX, "paldb_heart_icpt", "paldb-partition-global-0.dat"),
           os.path.join(FIX, "paldb_heart_icpt", "paldb-partition-global-1.dat"),
-          os.path.join(GAME, "feature-indexes", "paldb-partition-shard1-0.dat"),
-          os.path.join(GAME, "feature-indexes", "paldb-partition-shard2-0.dat"),
-          os.path.join(GAME, "feature-indexes", "paldb-partition-shard3-0.dat")]
+          game_store("shard1"), game_store("shard2"), game_store("shard3")]
 
 
 @pytest.mark.parametrize("path", STORES)
 def test_native_writer_reproduces_reference_stores_bytewise(path, tmp_path):
     import struct
     from photon_ml_amd.io.paldb import write_store_native
-    if not os.path.exists(path):
-        pytest.skip("reference store not present")
     kv = read_store(path)
     by_index = [k for _, k in sorted((v, k) for k, v in kv.items() if isinstance(k, str))]
     ref = open(path, "rb").read()
@@ -215,8 +212,6 @@ def test_native_writer_reproduces_reference_stores_bytewise(path, tmp_path):
 def test_native_reader_agrees_with_slot_enumeration(path):
     """Every key of a reference store found by PalDB's probe in the native reader, with the value the Python
     slot-enumerating reader decodes; absent keys give -1 / None."""
-    if not os.path.exists(path):
-        pytest.skip("reference store not present")
     d, f = os.path.split(path)
     ns = f[len("paldb-partition-"):-len("-0.dat")]
     n_parts = len([x for x in os.listdir(d) if x.startswith(f"paldb-partition-{ns}-")])
