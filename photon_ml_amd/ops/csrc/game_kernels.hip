@@ -208,7 +208,7 @@ struct CmpArgs {
   const uint32_t* pack;         // wide stream (interleaved)
   const void* val;
   const uint16_t* npack;        // narrow stream (interleaved 16-bit packs), one int32 base per round
-  const void* nval;
+  const void* nval;             // null: npack holds fused 16-B records (bf16 values; glm_kernels.hip TLNarrowSlot)
   const int* nbase;
   const unsigned char* keep;    // per chunk row: 1 = kept
   int* seg_cnt;                 // pass 0 output
@@ -246,9 +246,11 @@ __global__ __launch_bounds__(256) void tl_compact_kernel(CmpArgs a) {
       const int base = a.nbase[q];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const uint32_t p16 = a.npack[q * 256 + 4 * lane + k];
+        // fused records (nval null, 2-byte values): lane's 4 packs then its 4 values in one 16-B record
+        const long long pe = nval ? q * 256 + 4 * lane + k : q * 512 + 8 * lane + k;
+        const uint32_t p16 = a.npack[pe];
         p[k] = ((uint32_t)(base + (int)(p16 >> a.sbits)) << a.sbits) | (p16 & smask);
-        v[k] = nval[q * 256 + 4 * lane + k];
+        v[k] = nval ? nval[pe] : ((const VT*)a.npack)[pe + 4];
         ok[k] = true;
       }
     } else {

@@ -1013,7 +1013,35 @@ __device__ __forceinline__ void tl_stream_ring(const uint32_t* __restrict__ pack
 // slots under the code-generation rules of tl_stream_ring. Accumulation order per wave is fixed (deterministic).
 template <typename T> __device__ __forceinline__ T lane_bcast(T v, int src) { return __shfl(v, src, 64); }
 
-template <typename VT, typename XT, typename AT, bool SQ, int NW, int S = 2>
+// One ring slot of the narrow stream: the 4 packs and 4 values of a lane's quad, kept as loaded.
+// Two arrays (every value type; bf16 when the chunk was built with PML_TL_FUSE=0): an 8-B pack load at uint16
+// index e of ``npk`` plus the value quad at element e of ``nvl``.
+// FUSED RECORDS (bf16 values, the default; ops/tiled.py "fused narrow records"): both arrive in ONE 16-B load —
+// lane L of round r reads the record at ``npk`` + (r * 64 + L) * 16 bytes = {p0 | p1 << 16, p2 | p3 << 16,
+// v0 | v1 << 16, v2 | v3 << 16}, the same packs and values in the same order, so a round costs 2 vector-memory
+// instructions instead of 3 and no stream load is narrower than 16 B. ``nvl`` is null for such a chunk.
+template <typename VT, bool FUSED> struct TLNarrowSlot {
+  typedef typename TLVals<VT>::Raw Raw;
+  v2u pk;
+  Raw v;
+  __device__ __forceinline__ void load(const uint16_t* npk, const VT* nvl, size_t e) {
+    pk = ldg_nt((const v2u*)(npk + e));
+    v = TLVals<VT>::load(nvl + e);
+  }
+  __device__ __forceinline__ v2u packs() const { return pk; }
+  __device__ __forceinline__ Raw vals() const { return v; }
+};
+template <> struct TLNarrowSlot<uint16_t, true> {
+  typedef v2u Raw;
+  v4u rec;
+  __device__ __forceinline__ void load(const uint16_t* npk, const uint16_t*, size_t e) {
+    rec = ldg_nt((const v4u*)(npk + 2 * e));
+  }
+  __device__ __forceinline__ v2u packs() const { v2u p; p.x = rec.x; p.y = rec.y; return p; }
+  __device__ __forceinline__ Raw vals() const { v2u u; u.x = rec.z; u.y = rec.w; return u; }
+};
+
+template <typename VT, typename XT, typename AT, bool SQ, int NW, int S = 2, bool FUSED = false>
 __device__ __forceinline__ void tl_stream_narrow(const uint16_t* __restrict__ npk, const VT* __restrict__ nvl,
                                                  const int* __restrict__ nbs, int n_lo, int n_hi, int sbits,
                                                  const XT* __restrict__ x, AT* acc) {
@@ -1027,20 +1055,19 @@ __device__ __forceinline__ void tl_stream_narrow(const uint16_t* __restrict__ np
   if (r0 >= r1) return;
   const uint32_t smask = (1u << sbits) - 1u;
   const const_int_p bp = (const_int_p)nbs;
-  v2u pks[R];
-  Raw vs[R];
+  typedef TLNarrowSlot<VT, FUSED> Slot;
+  Slot sl[R];
   XT xs[R];
   const int abl = TL_ABL;
   AT regsum = AT(0);
-  auto issue = [&](int r, int base, v2u& pk, Raw& v, XT& xw) {
+  auto issue = [&](int r, int base, Slot& s, XT& xw) {
     const size_t e = (size_t)min(r, r1 - 1) * TL_ROUND + lane * TL_VEC;   // clamped re-read past the end
-    pk = ldg_nt((const v2u*)(npk + e));
-    v = TLVals<VT>::load(nvl + e);
+    s.load(npk, nvl, e);
     xw = (abl & 18) ? XT(1) : ldg(x + base + lane);
   };
 #pragma unroll
   for (int i = 0; i < S; ++i) {
-    issue(r0 + i, bp[min(r0 + i, r1 - 1)], pks[i], vs[i], xs[i]);
+    issue(r0 + i, bp[min(r0 + i, r1 - 1)], sl[i], xs[i]);
     __builtin_amdgcn_sched_barrier(0);
   }
   int nb = bp[min(r0 + S, r1 - 1)];
@@ -1048,13 +1075,13 @@ __device__ __forceinline__ void tl_stream_narrow(const uint16_t* __restrict__ np
 #pragma unroll
     for (int i = 0; i < R; ++i) {
       const int rc = r + i;
-      issue(rc + S, nb, pks[(i + S) % R], vs[(i + S) % R], xs[(i + S) % R]);   // slot of round rc - 1
+      issue(rc + S, nb, sl[(i + S) % R], xs[(i + S) % R]);   // slot of round rc - 1
       nb = bp[min(rc + S + 1, r1 - 1)];
       __builtin_amdgcn_sched_barrier(0);
       const bool live = rc < r1;          // tail rounds add an exact +0.0 (see tl_stream_ring)
       LT v[TL_VEC];
-      TLVals<VT>::get(vs[i], v);
-      const v2u pk = pks[i];
+      TLVals<VT>::get(sl[i].vals(), v);
+      const v2u pk = sl[i].packs();
       const uint32_t p[TL_VEC] = {pk.x & 0xffffu, pk.x >> 16, pk.y & 0xffffu, pk.y >> 16};
 #pragma unroll
       for (int k = 0; k < TL_VEC; ++k) {
@@ -1088,7 +1115,21 @@ __device__ __forceinline__ void tl_stream(const uint32_t* __restrict__ pack, con
 }
 
 // Narrow-section streams of one chunk (see tl_stream_narrow); n_lo == n_hi: the unit has no narrow rounds.
+// ``val`` null: ``pack`` is a stream of fused 16-B records (bf16 values only, TLNarrowSlot).
 struct TLNarrow { const uint16_t* pack; const void* val; const int* base; const int* wbase; };
+
+// The narrow rounds [n_lo, n_hi) of one unit in the chunk's narrow layout (a scalar, wave-uniform choice).
+template <typename VT, typename XT, typename AT, bool SQ, int NW, int S>
+__device__ __forceinline__ void tl_narrow(const TLNarrow& nar, int n_lo, int n_hi, int sbits,
+                                          const XT* __restrict__ x, AT* acc) {
+  if constexpr (sizeof(VT) == 2) {
+    if (nar.val == nullptr) {
+      tl_stream_narrow<VT, XT, AT, SQ, NW, S, true>(nar.pack, nullptr, nar.base, n_lo, n_hi, sbits, x, acc);
+      return;
+    }
+  }
+  tl_stream_narrow<VT, XT, AT, SQ, NW, S, false>(nar.pack, (const VT*)nar.val, nar.base, n_lo, n_hi, sbits, x, acc);
+}
 
 // Forward over row blocks. blk: 6 ints per block {row_lo, nrows, e_lo, e_hi, n_lo, n_hi} (chunk-local).
 template <typename VT, typename XT, typename RT, typename AT, int MAXR, int U, int NW, int P>
@@ -1103,9 +1144,7 @@ __device__ __forceinline__ void tl_fwd_block(int b, int row_lo, int nrows, int e
     for (int w = 0; w < NW; ++w) acc[w][i] = AT(0);
   __syncthreads();
   if (n_hi > n_lo)
-    tl_stream_narrow<VT, XT, AT, false, NW, (P >= 5 ? 4 : 2)>(nar.pack, (const VT*)nar.val, nar.base, n_lo, n_hi,
-                                                              rbits, x,
-                                            acc[threadIdx.x >> 6]);
+    tl_narrow<VT, XT, AT, false, NW, (P >= 5 ? 4 : 2)>(nar, n_lo, n_hi, rbits, x, acc[threadIdx.x >> 6]);
   tl_stream<VT, XT, AT, false, U, NW, P>(pack, val, x, e_lo, e_hi, rbits, acc[threadIdx.x >> 6], nar.wbase);
   __syncthreads();
   double F = 0.0, S = 0.0;
@@ -1140,7 +1179,8 @@ __global__ __launch_bounds__(NW * 64) void tl_fwd_kernel(const int* __restrict__
 
 // All chunks of a shard in ONE launch (no per-chunk tails / launch gaps): block table of 8 ints
 // {chunk, global row_lo, nrows, e_lo, e_hi, col_lo, n_lo, n_hi}; per-chunk stream pointers in device arrays
-// (ptrs[6 * chunk + {0: pack, 1: val, 2: narrow pack, 3: narrow val, 4: narrow base, 5: wide-round bases or 0}]);
+// (ptrs[6 * chunk + {0: pack, 1: val, 2: narrow pack (or fused records), 3: narrow val (0: fused records),
+// 4: narrow base, 5: wide-round bases or 0}]);
 // row-data pointers in ``a``
 // are shard-global; stats index = global block index.
 template <typename VT, typename XT, typename RT, typename AT, int MAXR, int U, int NW, int P>
@@ -1173,9 +1213,7 @@ __device__ __forceinline__ void tl_t_item(int tile, int e_lo, int e_hi, int part
     for (int w = 0; w < NW; ++w) acc[w][i] = AT(0);
   __syncthreads();
   if (n_hi > n_lo)
-    tl_stream_narrow<VT, XT, AT, SQ, NW, (P >= 5 ? 4 : 2)>(nar.pack, (const VT*)nar.val, nar.base, n_lo, n_hi,
-                                                           cbits, x,
-                                         acc[threadIdx.x >> 6]);
+    tl_narrow<VT, XT, AT, SQ, NW, (P >= 5 ? 4 : 2)>(nar, n_lo, n_hi, cbits, x, acc[threadIdx.x >> 6]);
   tl_stream<VT, XT, AT, SQ, U, NW, P>(pack, val, x, e_lo, e_hi, cbits, acc[threadIdx.x >> 6], nar.wbase);
   __syncthreads();
   const int c0 = tile << cbits;

@@ -301,6 +301,9 @@ class DeviceGLMData(GLMComputable):
             base = ch.nbase.cpu().to(torch.int64)
             if ch.npack.numel() < 256 * nrounds or ch.nval.numel() < 256 * nrounds:
                 raise ValueError(f"chunk {c}: {what} narrow stream shorter than its rounds")
+            if ch.fused and (ch.nrec.numel() < 512 * nrounds or ch.val.element_size() != 2
+                             or not ch.nrec.is_contiguous()):
+                raise ValueError(f"chunk {c}: {what} fused narrow records need 2-byte values, 16 B per lane and round")
             if int(base.min()) < 0 or int(base.max()) + 64 > xlen:
                 raise ValueError(f"chunk {c}: {what} narrow key window outside the gathered vector")
 

@@ -21,6 +21,14 @@ values with cross-lane permutes (``tl_stream_narrow``): 4 B/entry of stream inst
 gather instructions. Unit tables gain ``{n_lo, n_hi}`` (the unit's narrow rounds); a unit's narrow rounds are
 processed before its remaining (wide) entries, both in sorted order.
 
+FUSED NARROW RECORDS (``PML_TL_FUSE``, default on; bf16 values only): the narrow section is ONE stream of 16-byte
+lane records instead of a pack array and a value array — lane L of narrow round r reads the record at byte
+``(r * 64 + L) * 16``, eight 16-bit words ``{p0, p1, p2, p3, v0, v1, v2, v3}``: its four packs, then the bit
+patterns of its four bf16 values, in the interleaved order (logical entries L, L+64, L+128, L+192 of the round).
+Same entries in the same order; a narrow round then costs one 16-byte stream load per lane instead of two 8-byte
+ones. ``npack`` / ``nval`` of such a chunk are strided views into the record stream ``nrec`` and the kernels get a
+null narrow-value pointer. fp32 / fp64 chunks (16-byte value quads already) keep the two arrays.
+
 Both copies are stored LANE-INTERLEAVED by default (``il``; ``PML_TL_IL=0`` keeps the plain order): every work
 unit (forward block / transpose item) starts on a 256-entry round boundary and is zero-padded to whole rounds,
 and inside a round the 16-B quad of lane L holds the unit's sorted entries L, L+64, L+128, L+192, so each gather
@@ -86,6 +94,7 @@ TL_VEC = 4               # entries per lane per round
 INTERLEAVE = int(os.environ.get("PML_TL_IL", "1"))
 NARROW = int(os.environ.get("PML_TL_NARROW", "1"))
 NARROW_W = 64            # key window loaded per narrow round (one wave64 load)
+FUSE = int(os.environ.get("PML_TL_FUSE", "1"))   # bf16 narrow rounds as fused 16-byte lane records
 WIDE_BASE = int(os.environ.get("PML_TL_WIDE_BASE", "1"))   # per-round key bases for wide shards (TLFwdChunk)
 
 
@@ -196,7 +205,9 @@ def split_narrow(pack: torch.Tensor, val: torch.Tensor, n: torch.Tensor, sbits: 
     ``pack`` (int64, low 32 bits = the packed entry ``key << sbits | slot``) and ``val`` hold units of ``n[u]``
     consecutive entries, each unit sorted by key. Returns ``(wide_pack, wide_val, wide_n, npack, nval, nbase,
     nrounds)``: the remaining entries per unit (same order), the interleaved 16-bit narrow stream (int16 bit
-    patterns), its values, one base per narrow round and the number of narrow rounds per unit."""
+    patterns), its values, one base per narrow round and the number of narrow rounds per unit. bf16 values with
+    ``FUSE``: ``npack`` is the fused record stream (int16, 8 words per lane: 4 packs, 4 value bit patterns) and
+    ``nval`` is None."""
     dev = pack.device
     n = n.to(torch.int64)
     U = n.numel()
@@ -221,6 +232,9 @@ def split_narrow(pack: torch.Tensor, val: torch.Tensor, n: torch.Tensor, sbits: 
     il = lambda t: t.reshape(-1, TL_VEC, 64).transpose(1, 2).reshape(-1)
     npack = il(torch.where(p16 >= 32768, p16 - 65536, p16).to(torch.int16)).contiguous()
     nval = il(val[idx]).contiguous()
+    if FUSE and val.dtype == torch.bfloat16:
+        npack = torch.cat([npack.view(-1, TL_VEC), nval.view(torch.int16).view(-1, TL_VEC)], 1).reshape(-1)
+        nval = None
     nbase = base.to(torch.int32).contiguous()
     # narrow rounds per unit: gu is non-decreasing (units' rounds are consecutive), so a prefix sum of the flags read
     # at the unit boundaries (torch.bincount on these long runs of one bin serialised its atomics)
@@ -239,12 +253,16 @@ def narrow_logical(npack: torch.Tensor, nval: torch.Tensor, nbase: torch.Tensor,
     """(pack32 as int64, val) of narrow rounds [r_lo, r_hi) in logical order."""
     r = torch.arange(int(r_lo), int(r_hi), device=npack.device)
     if not r.numel():
-        return torch.zeros(0, dtype=torch.int64, device=npack.device), nval[:0]
+        return torch.zeros(0, dtype=torch.int64, device=npack.device), nval[:0].reshape(-1)
     ph = (r[:, None] * IL_ROUND + torch.arange(IL_ROUND, device=npack.device)[None, :]).reshape(-1, 64, TL_VEC)
     ph = ph.transpose(1, 2).reshape(-1)          # physical position of logical entry t of each round
-    p16 = npack[ph].to(torch.int64) & 0xFFFF
+    # (a fused chunk passes its strided views into the record stream: position 4 L + k = word k of lane L's record)
+    rl, rh = int(r_lo) * IL_ROUND, int(r_hi) * IL_ROUND
+    ph = ph - rl
+    p16 = npack.reshape(-1, TL_VEC)[rl // TL_VEC:rh // TL_VEC].reshape(-1)[ph].to(torch.int64) & 0xFFFF
     base = nbase[r].to(torch.int64).repeat_interleave(IL_ROUND)
-    return (((p16 >> sbits) + base) << sbits) | (p16 & ((1 << sbits) - 1)), nval[ph]
+    return ((((p16 >> sbits) + base) << sbits) | (p16 & ((1 << sbits) - 1)),
+            nval.reshape(-1, TL_VEC)[rl // TL_VEC:rh // TL_VEC].reshape(-1)[ph])
 
 
 class _NarrowMixin:
@@ -253,11 +271,23 @@ class _NarrowMixin:
 
     wbase = None          # forward copies only: int32 key base per physical wide round (see TLFwdChunk)
 
+    nrec = None           # fused chunks: the record stream (int16, 8 words per lane record)
+
     def _set_narrow(self, npack, nval, nbase):
+        """``nval`` None: ``npack`` is the fused record stream (``split_narrow``); the kernels tell the layouts
+        apart by the null value pointer."""
         from .native import TLNarrow
+        self.nrec = npack if nval is None else None
+        if nval is None:
+            rec = npack.view(-1, 2 * TL_VEC)
+            npack, nval = rec[:, :TL_VEC], rec[:, TL_VEC:].view(torch.bfloat16)
         self.npack, self.nval, self.nbase = npack, nval, nbase
-        self.nar = TLNarrow(npack.data_ptr(), nval.data_ptr(), nbase.data_ptr(),
+        self.nar = TLNarrow(npack.data_ptr(), None if self.fused else nval.data_ptr(), nbase.data_ptr(),
                             None if self.wbase is None else self.wbase.data_ptr())
+
+    @property
+    def fused(self) -> bool:
+        return self.nrec is not None
 
     @property
     def n_narrow_rounds(self) -> int:
@@ -674,12 +704,12 @@ class TLTMulti:
 
 
 def stream_ptr_table(chunks, device) -> torch.Tensor:
-    """Per-chunk stream pointers of the shard-wide kernels: {pack, val, narrow pack, narrow val, narrow base,
-    wide-round bases (0: absolute keys)}."""
+    """Per-chunk stream pointers of the shard-wide kernels: {pack, val, narrow pack (fused chunks: the record
+    stream), narrow val (0: fused records), narrow base, wide-round bases (0: absolute keys)}."""
     wb = lambda ch: 0 if getattr(ch, "wbase", None) is None else ch.wbase.data_ptr()
-    return torch.tensor([[ch.pack.data_ptr(), ch.val.data_ptr(), ch.npack.data_ptr(), ch.nval.data_ptr(),
-                          ch.nbase.data_ptr(), wb(ch)] for ch in chunks], dtype=torch.int64,
-                        device=device).reshape(-1)
+    return torch.tensor([[ch.pack.data_ptr(), ch.val.data_ptr(), ch.npack.data_ptr(),
+                          0 if ch.fused else ch.nval.data_ptr(), ch.nbase.data_ptr(), wb(ch)] for ch in chunks],
+                        dtype=torch.int64, device=device).reshape(-1)
 
 
 # ---- row-sampled copies (K20 down-sampling work saving: DeviceGLMData.row_sampled) ---------------------------
@@ -739,7 +769,8 @@ class RowCompaction:
         self._keep_alive = (seg, table, keep)
         self.args = CmpArgs(table.data_ptr(), lo, 0 if forward else -1, seg.data_ptr(), S, ch._sbits,
                             0 if forward else 1, ch.pack.data_ptr(), ch.val.data_ptr(), ch.npack.data_ptr(),
-                            ch.nval.data_ptr(), ch.nbase.data_ptr(), keep.data_ptr(), self.seg_cnt.data_ptr(),
+                            None if ch.fused else ch.nval.data_ptr(), ch.nbase.data_ptr(), keep.data_ptr(),
+                            self.seg_cnt.data_ptr(),
                             None, None, None, None)
         self.lib, self.stream = require_game_lib(), stream_handle(dev)
         self.vbytes = ch.val.element_size()

@@ -27,6 +27,8 @@ def main():
     ap.add_argument("--configs", default="0,1,8192", help="semicolon list of fwd_strided,t_strided,hot_n")
     ap.add_argument("--il", type=int, nargs="+", default=[1], help="tiled stream order(s): 1 lane-interleaved, 0 plain")
     ap.add_argument("--narrow", type=int, nargs="+", default=[1], help="narrow rounds (16-bit packs) off/on")
+    ap.add_argument("--fuse", type=int, nargs="+", default=[1],
+                    help="bf16 narrow rounds as fused 16-byte records (PML_TL_FUSE) off/on; repeat values to alternate")
     args = ap.parse_args()
     res = []
     from photon_ml_amd.ops.native import glm_lib, configure
@@ -36,17 +38,18 @@ def main():
         configs = [("tl",) + tuple(int(v) for v in c.split(",")) for c in args.tl_configs.split(";")]
     cache = {}
     from photon_ml_amd.ops import tiled
-    for cr, il, nar, abl, cfg in [(c, i, n, a, g) for c in args.chunk_rows for i in args.il for n in args.narrow
-                                  for a in args.ablate for g in configs]:
+    for cr, il, nar, fuse, abl, cfg in [(c, i, n, f, a, g) for c in args.chunk_rows for i in args.il
+                                        for n in args.narrow for f in args.fuse for a in args.ablate for g in configs]:
         lib.pml_set_ablate(0)
-        if (cr, il, nar) not in cache:
+        if (cr, il, nar, fuse) not in cache:
             cache.clear()
             torch.cuda.empty_cache()
             tiled.INTERLEAVE = il
             tiled.NARROW = nar
-            cache[(cr, il, nar)] = generate_device_shard(args.rows, args.features, args.nnz, "cuda", args.precision,
-                                                         chunk_rows=cr, layout=args.layout)
-        data, w = cache[(cr, il, nar)]
+            tiled.FUSE = fuse
+            cache[(cr, il, nar, fuse)] = generate_device_shard(args.rows, args.features, args.nnz, "cuda",
+                                                               args.precision, chunk_rows=cr, layout=args.layout)
+        data, w = cache[(cr, il, nar, fuse)]
         lib.pml_set_ablate(abl)
         if cfg[0] == "tl":
             configure(tl_waves=cfg[1], tl_waves_t=cfg[2], tl_pipe=cfg[3],
@@ -78,7 +81,7 @@ def main():
             data.value_grad_packed(LOGISTIC, w * 0.1, 0.0)
         torch.cuda.synchronize()
         tp = (time.perf_counter() - t0) / args.reps * 1e3
-        r = {"cfg": cfg, "il": il, "narrow": nar, "ablate": abl,
+        r = {"cfg": cfg, "il": il, "narrow": nar, "fuse": fuse, "ablate": abl,
              "fwd_stream_GB": sum(c.nbytes() for c in data.csr) / 1e9,
              "t_stream_GB": sum(c.nbytes() for c in data.csc) / 1e9,
              "narrow_frac_fwd": 256 * sum(getattr(c, "n_narrow_rounds", 0) for c in data.csr) / max(1, sum(c.nnz for c in data.csr)),
