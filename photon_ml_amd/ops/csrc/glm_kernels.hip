@@ -1397,6 +1397,16 @@ static int g_tl_deep_t = 0;    // interleaved transpose: same
 #define TL_WAVES_T 4
 #endif
 
+// LDS accumulator type by block / tile width, the same for the per-chunk and the shard-wide entry points. Up to
+// 11 bits the accumulators are fp64 (always for fp64 data; bf16 / fp32 data: unless the experiment build's tl_acc64
+// knob is off). 4096 fp64 slots per wave do not fit the 64 KB of a work-group (transpose: 4 waves x 32 KB), so
+// width 12 exists for bf16 / fp32 data only and accumulates in fp32 (4 waves x 16 KB); fp64 data stop at 11 bits
+// (TL_MAXBITS_F64 in ops/tiled.py).
+template <typename XT> static inline int tl_maxbits() { return sizeof(XT) == 8 ? 11 : TL_MAXBITS; }
+template <typename XT> static inline bool tl_acc64(int bits) {
+  return sizeof(XT) == 8 || (bits <= 11 && !TL_KNOB(!g_tl_acc64));
+}
+
 template <typename VT, typename XT, typename RT, typename AT, int MAXR>
 static void tl_fwd_launch(const TLFwdDesc* c, const void* x, FwdArgs<XT, RT> a, double* stats, hipStream_t st) {
 #define TLF(NW, P) hipLaunchKernelGGL((tl_fwd_kernel<VT, XT, RT, AT, MAXR, 2, NW, P>), dim3(c->nblk), dim3(NW * 64), 0, \
@@ -1431,14 +1441,16 @@ template <typename VT, typename XT, typename RT>
 static int tl_fwd_multi_impl(const TLFwdMultiDesc* c, const void* x, FwdArgs<XT, RT> a, double* stats,
                              hipStream_t st) {
   if (c->nblk <= 0) return 0;
-  if (c->rbits < 1 || c->rbits > 11) return -22;
-  const bool f64 = sizeof(XT) == 8 || !TL_KNOB(!g_tl_acc64);
-  if (f64) {
+  if (c->rbits < 1 || c->rbits > tl_maxbits<XT>()) return -22;
+  if (tl_acc64<XT>(c->rbits)) {
     if (c->rbits <= 10) tl_fwd_multi_launch<VT, XT, RT, double, 1024>(c, x, a, stats, st);
     else tl_fwd_multi_launch<VT, XT, RT, double, 2048>(c, x, a, stats, st);
+  } else if (c->rbits <= 10) {
+    tl_fwd_multi_launch<VT, XT, RT, float, 1024>(c, x, a, stats, st);
+  } else if (c->rbits == 11) {
+    tl_fwd_multi_launch<VT, XT, RT, float, 2048>(c, x, a, stats, st);
   } else {
-    if (c->rbits <= 10) tl_fwd_multi_launch<VT, XT, RT, float, 1024>(c, x, a, stats, st);
-    else tl_fwd_multi_launch<VT, XT, RT, float, 2048>(c, x, a, stats, st);
+    tl_fwd_multi_launch<VT, XT, RT, float, 4096>(c, x, a, stats, st);
   }
   LAUNCH_CHECK();
   return 0;
@@ -1447,10 +1459,8 @@ static int tl_fwd_multi_impl(const TLFwdMultiDesc* c, const void* x, FwdArgs<XT,
 template <typename VT, typename XT, typename RT>
 static int tl_fwd_impl(const TLFwdDesc* c, const void* x, FwdArgs<XT, RT> a, double* stats, hipStream_t st) {
   if (c->nblk <= 0) return 0;
-  if (c->rbits < 1 || c->rbits > TL_MAXBITS) return -22;
-  const bool f64 = sizeof(XT) == 8 || !TL_KNOB(!g_tl_acc64);
-  if (f64) {
-    if (c->rbits > 11) return -22;  // fp64 LDS: 4 waves x 2048 rows = 64 KB
+  if (c->rbits < 1 || c->rbits > tl_maxbits<XT>()) return -22;
+  if (tl_acc64<XT>(c->rbits)) {
     if (c->rbits <= 10) tl_fwd_launch<VT, XT, RT, double, 1024>(c, x, a, stats, st);
     else tl_fwd_launch<VT, XT, RT, double, 2048>(c, x, a, stats, st);
   } else if (c->rbits <= 10) {
@@ -1481,10 +1491,8 @@ static void tl_t_launch(const TLTDesc* c, const void* x, double* G, double* part
 template <typename VT, typename XT, bool SQ>
 static int tl_t_impl(const TLTDesc* c, const void* x, double* G, double* parts, hipStream_t st) {
   if (c->nitems <= 0) return 0;
-  if (c->cbits < 1 || c->cbits > TL_MAXBITS) return -22;
-  const bool f64 = sizeof(XT) == 8 || !TL_KNOB(!g_tl_acc64);
-  if (f64) {
-    if (c->cbits > 11) return -22;
+  if (c->cbits < 1 || c->cbits > tl_maxbits<XT>()) return -22;
+  if (tl_acc64<XT>(c->cbits)) {
     if (c->cbits <= 10) tl_t_launch<VT, XT, double, SQ, 1024>(c, x, G, parts, st);
     else tl_t_launch<VT, XT, double, SQ, 2048>(c, x, G, parts, st);
   } else if (c->cbits <= 10) {
@@ -1525,15 +1533,16 @@ static void tl_t_multi_launch(const TLTMultiDesc* c, const void* x, double* G, d
 template <typename VT, typename XT, bool SQ>
 static int tl_t_multi_impl(const TLTMultiDesc* c, const void* x, double* G, double* parts, hipStream_t st) {
   if (c->nitems <= 0) return 0;
-  if (c->cbits < 1 || c->cbits > 11) return -22;
-  const bool f64 = sizeof(XT) == 8 || !TL_KNOB(!g_tl_acc64);
-  if (f64) {
+  if (c->cbits < 1 || c->cbits > tl_maxbits<XT>()) return -22;
+  if (tl_acc64<XT>(c->cbits)) {
     if (c->cbits <= 10) tl_t_multi_launch<VT, XT, double, SQ, 1024>(c, x, G, parts, st);
     else tl_t_multi_launch<VT, XT, double, SQ, 2048>(c, x, G, parts, st);
   } else if (c->cbits <= 10) {
     tl_t_multi_launch<VT, XT, float, SQ, 1024>(c, x, G, parts, st);
-  } else {
+  } else if (c->cbits == 11) {
     tl_t_multi_launch<VT, XT, float, SQ, 2048>(c, x, G, parts, st);
+  } else {
+    tl_t_multi_launch<VT, XT, float, SQ, 4096>(c, x, G, parts, st);
   }
   LAUNCH_CHECK();
   if (c->nmt > 0) {
