@@ -198,8 +198,12 @@ class GameEstimator:
 
     def _validation_evaluators(self, validation: GameData):
         names = self.validation_evaluators or [default_validation_evaluator(self.training_task)]
-        return [build_evaluator(parse_evaluator_type(n), validation.response, validation.offsets, validation.weights,
-                                validation.id_tags) for n in names]
+        # per-group metrics (AUC:tag, PRECISION@k:tag) live on the training device: their kernels read the scores
+        # where score_rows_kernel wrote them; the simple evaluators keep their placement
+        dev = self.device if self.device is not None else default_device()
+        types = [parse_evaluator_type(n) for n in names]
+        return [build_evaluator(t, validation.response, validation.offsets, validation.weights, validation.id_tags,
+                                device=dev if t.is_multi else None) for t in types]
 
     def fit(self, data: GameData, validation: Optional[GameData],
             configurations: Sequence[Dict[str, GLMOptimizationConfiguration]]) -> List[GameResult]:
@@ -254,14 +258,17 @@ class GameTransformer:
 
     def transform(self, data: GameData):
         """Return (scores WITHOUT offsets, evaluations or None)."""
-        return self._evaluate(data, self.model.score(data, self.device))
+        return self._evaluate(data, self.model.score(data, self.device), self.device)
 
-    def _evaluate(self, data: GameData, scores):
+    def _evaluate(self, data: GameData, scores, multi_device=None):
+        """``multi_device``: where the per-group evaluators live (None: with the labels, on the host)."""
         evals = None
         if self.validation_evaluators:
             evals = []
             for n in self.validation_evaluators:
-                e = build_evaluator(parse_evaluator_type(n), data.response, data.offsets, data.weights, data.id_tags)
+                t = parse_evaluator_type(n)
+                e = build_evaluator(t, data.response, data.offsets, data.weights, data.id_tags,
+                                    device=multi_device if t.is_multi else None)
                 evals.append((e, e.evaluate(scores)))
         return scores, evals
 

@@ -12,7 +12,8 @@ Reference: ``photon-lib/.../evaluation/{Evaluator,EvaluatorType}.scala`` (evalua
   * name parsing ``AUC``, ``RMSE``, ``LOGISTIC_LOSS``, ..., ``PRECISION@5:queryId``, ``AUC:userId``.
 
 Sorting-based metrics run on the device (torch sort / segmented reductions), so the whole validation pass stays
-in HBM.
+in HBM; the per-group metrics of a single-process GPU run are HIP kernels over a group layout built once
+(``segmented.py``), under a process group they gather their columns through the host.
 """
 from __future__ import annotations
 
@@ -198,11 +199,44 @@ class MultiEvaluator(Evaluator):
             uniq, inv = np.unique(ids.astype(str) if ids.dtype == object else ids, return_inverse=True)
         self.group = torch.as_tensor(inv, dtype=torch.int64, device=self.labels.device)
         self.n_groups = len(uniq)
+        self.group_keys = uniq
+        self.last_path = "host"
+        # single-process GPU runs evaluate every group in HIP kernels over a layout built once (K12); under a
+        # process group the columns are gathered through the host and evaluated by the loop below
+        self.ranking = None
+        if self.labels.is_cuda and not self.distributed:
+            from .segmented import GroupedRanking
+            self.ranking = GroupedRanking(self.group, self.labels, self.weights, self.labels.device)
 
     def _local(self, s, y, w) -> float:
         raise NotImplementedError
 
+    def _device_values(self, s) -> Optional[torch.Tensor]:
+        """Per-group values from the HIP kernels; None when they decline (a NaN score)."""
+        raise NotImplementedError
+
+    def _values(self, s):
+        """The metric of every group, NaN where it is undefined: an fp64 device tensor from the HIP kernels
+        (``last_path == "device"``) or a list of floats from the host loop (``"host"``)."""
+        vals = self._device_values(s) if self.ranking is not None else None
+        self.last_path = "host" if vals is None else "device"
+        return self._host_values(s) if vals is None else vals
+
+    def evaluate_groups(self, scores):
+        """``(group_keys, values)``: the sorted distinct group ids (their stable hashes under a process group, where
+        every rank must call this) and the local metric of every group for ``scores + offsets`` as an fp64 tensor
+        on the evaluator's device, NaN where it is undefined."""
+        vals = self._values(_t(scores, self.labels.device) + self.offsets)
+        return self.group_keys, torch.as_tensor(vals, dtype=torch.float64, device=self.labels.device)
+
     def _evaluate(self, s):
+        vals = self._values(s)
+        if self.last_path == "device":
+            return self.ranking.mean_finite(vals)
+        vals = [v for v in vals if math.isfinite(v)]
+        return float(np.mean(vals)) if vals else float("nan")
+
+    def _host_values(self, s) -> List[float]:
         order = torch.argsort(self.group, stable=True)
         g = self.group[order]
         if self.distributed:
@@ -211,15 +245,13 @@ class MultiEvaluator(Evaluator):
             s, y, w = s[order], self.labels[order], self.weights[order]
         counts = torch.bincount(g, minlength=self.n_groups).cpu().numpy()
         starts = np.concatenate([[0], np.cumsum(counts)])
-        vals = []
+        vals = [float("nan")] * self.n_groups
         s_c, y_c, w_c = s.cpu(), y.cpu(), w.cpu()
         for i in range(self.n_groups):
             a, b = starts[i], starts[i + 1]
             if b > a:
-                v = self._local(s_c[a:b], y_c[a:b], w_c[a:b])
-                if math.isfinite(v):
-                    vals.append(v)
-        return float(np.mean(vals)) if vals else float("nan")
+                vals[i] = self._local(s_c[a:b], y_c[a:b], w_c[a:b])
+        return vals
 
 
 class AUCMultiEvaluator(MultiEvaluator):
@@ -230,6 +262,9 @@ class AUCMultiEvaluator(MultiEvaluator):
 
     def _local(self, s, y, w):
         return auc_weighted(s, y, w)
+
+    def _device_values(self, s):
+        return self.ranking.auc(s)
 
 
 class PrecisionAtKMultiEvaluator(MultiEvaluator):
@@ -243,6 +278,9 @@ class PrecisionAtKMultiEvaluator(MultiEvaluator):
 
     def _local(self, s, y, w):
         return precision_at_k(s, y, self.k)
+
+    def _device_values(self, s):
+        return self.ranking.precision_at_k(s, self.k)
 
 
 # --------------------------------------------------------------------------------------------------------------

@@ -11,6 +11,8 @@
 //     random projection (projector/ProjectionMatrix.scala:95-124);
 // * spmm_rows_kernel — K15 forward random projection X P^T of sparse rows (ProjectionMatrix.scala:48-63).
 // * downsample_kernel — K20 fixed-effect down-sampling as an on-device weight rewrite.
+// * seg_rank_wave_kernel / seg_rank_block_kernel — K12 per-group AUC and precision@k (AUC:tag, PRECISION@k:tag):
+//   every group sorted in registers / LDS and evaluated in one pass, one launch per size class.
 //
 // Built with: hipcc --offload-arch=gfx950 -O3 -shared -fPIC (photon_ml_amd/ops/build.py). C ABI, ctypes.
 
@@ -540,9 +542,304 @@ __global__ __launch_bounds__(256) void csr_gather_rows_kernel(const long long* _
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// K12 per-group ranking metrics (AUC:tag, PRECISION@k:tag; evaluation/segmented.py): one fp64 value per group of a
+// group-ordered row layout (seg_ptr over groups, perm = row position of every group-ordered slot, group-ordered
+// weights and positive flags). Groups are bucketed by length on the host and every bucket has its own execution:
+//   C16 (1..16 rows)   seg_rank_wave_kernel<16>: four groups per wave, one 16-lane row each, rows in registers
+//   C64 (17..64)       seg_rank_wave_kernel<64>: one wave per group, rows in registers
+//   CWG (65..4096)     seg_rank_block_kernel<false>: one 256-thread workgroup per group, bitonic sort in LDS
+//                      (8 B score + 4 B local index per padded row: 48 KB at 4096)
+//   LONG (> wg_max)    seg_rank_block_kernel<true>: rows arrive sorted (two stable torch sorts on the host side of
+//                      the wrapper), one workgroup streams its group in chunks of 256 rows
+// Order: score descending, ties by position within the group ascending (a total order, so the bitonic network need
+// not be stable; the tie test is ==, so -0.0 ties with 0.0). Padding rows: score -inf, weight 0, index past the end.
+// AUC is the tie-grouped weighted trapezoid of AreaUnderROCCurveLocalEvaluator.scala:33-70: a tie group with
+// positive / negative weight gp / gn that closes at sorted row i adds (P_i - gp) gn + gp gn / 2, P_i the inclusive
+// positive prefix; gp, gn are segmented scans (sums of non-negative terms, no differences of prefixes of gn), the
+// value is raw / (tp * tn) in exactly that expression (NaN when a class is missing). Precision@k counts positives
+// among the first min(k, L) sorted rows, over k. No atomics: scans and reductions are fixed shuffle / LDS trees, so
+// every launch gives the same bits. A NaN score sets *nan_flag (all writers store 1) and the wrapper discards the
+// result; the compare-exchange evaluates ONE predicate per pair on both sides, so even then the indices stay a
+// permutation and nothing is read out of bounds.
+// ---------------------------------------------------------------------------------------------------------------
+struct SegRankArgs {
+  const long long* seg_ptr;     // [n_groups + 1] (unused by the pre-sorted kernel)
+  const long long* perm;        // [n_rows] row position of every group-ordered slot (unused when pre-sorted)
+  const double* scores;         // [n_rows] in row order; pre-sorted: the LONG rows' scores in sorted order
+  const double* wts;            // [n_rows] group-ordered; pre-sorted: sorted order
+  const unsigned char* flag;    // positive flags, same order as wts
+  const long long* list;        // [n_list] group indices of this class
+  const long long* lptr;        // pre-sorted only: [n_list + 1] row range of every listed group
+  double* out;                  // [n_groups]
+  int* nan_flag;
+  long long n_list, n_rows, n_groups;
+  int k;                        // precision@k position (AUC: ignored)
+};
+
+#define SR_THREADS 256
+#define SR_WG_MAX 4096
+
+__device__ __forceinline__ bool sr_before(double sa, int ia, double sb, int ib) {
+  return sa > sb || (sa == sb && ia < ib);
+}
+
+template <int W, bool AUC>
+__global__ __launch_bounds__(SR_THREADS) void seg_rank_wave_kernel(SegRankArgs a) {
+  const int l = threadIdx.x % W;
+  const long long b = (long long)blockIdx.x * (SR_THREADS / W) + threadIdx.x / W;
+  // every lane of a W-lane row takes part in the shuffles: an idle or malformed group runs with L = 0
+  long long g = -1, r0 = 0;
+  int L = 0;
+  if (b < a.n_list) {
+    g = a.list[b];
+    if (g >= 0 && g < a.n_groups) {
+      r0 = a.seg_ptr[g];
+      const long long len = a.seg_ptr[g + 1] - r0;
+      if (len >= 1 && len <= W && r0 >= 0 && r0 + len <= a.n_rows) L = (int)len;
+    } else {
+      g = -1;
+    }
+  }
+  double s = -INFINITY, w = 0.0;
+  bool fl = false;
+  if (l < L) {
+    const long long pr = a.perm[r0 + l];
+    s = (pr >= 0 && pr < a.n_rows) ? a.scores[pr] : (double)NAN;
+    w = a.wts[r0 + l];
+    fl = a.flag[r0 + l] != 0;
+    if (s != s) *a.nan_flag = 1;
+  }
+  int idx = l;
+#pragma unroll
+  for (int k = 2; k <= W; k <<= 1) {
+#pragma unroll
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      const double so = __shfl_xor(s, j, W);
+      const int io = __shfl_xor(idx, j, W);
+      const bool up = (l & k) == 0;
+      const bool c = (l & j) == 0 ? sr_before(s, idx, so, io) : sr_before(so, io, s, idx);   // lower before upper?
+      if (c != up) { s = so; idx = io; }
+    }
+  }
+  const double p0 = fl ? w : 0.0;
+  const double n0 = w - p0;
+  double val;
+  if (AUC) {
+    const double p = __shfl(p0, idx, W), n = __shfl(n0, idx, W);
+    const double sp = __shfl_up(s, 1, W), sn = __shfl_down(s, 1, W);
+    // padding rows (-inf, weight 0) take part as ordinary rows: they add 0 to whatever tie group they join
+    bool f = l == 0 || s != sp;
+    const bool tail = l == W - 1 || s != sn;
+    double gp = p, gn = n, P = p;
+#pragma unroll
+    for (int d = 1; d < W; d <<= 1) {
+      const double tgp = __shfl_up(gp, d, W), tgn = __shfl_up(gn, d, W), tP = __shfl_up(P, d, W);
+      const int tf = __shfl_up((int)f, d, W);
+      if (l >= d) {
+        P += tP;
+        if (!f) { gp += tgp; gn += tgn; f = tf != 0; }
+      }
+    }
+    double raw = tail ? (P - gp) * gn + gp * gn / 2.0 : 0.0;
+    double tp = p, tn = n;
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) {
+      raw += __shfl_xor(raw, o, W);
+      tp += __shfl_xor(tp, o, W);
+      tn += __shfl_xor(tn, o, W);
+    }
+    val = raw / (tp * tn);
+  } else {
+    const int fs = __shfl((int)fl, idx, W);
+    int hit = (l < a.k && l < L) ? fs : 0;
+#pragma unroll
+    for (int o = W / 2; o > 0; o >>= 1) hit += __shfl_xor(hit, o, W);
+    val = (double)hit / (double)a.k;
+  }
+  if (l == 0 && g >= 0) a.out[g] = L > 0 ? val : (double)NAN;
+}
+
+// CWG (PRE = false): sort the group in LDS, then evaluate the sorted rows in chunks of 256. LONG (PRE = true): the
+// rows are already sorted, the same chunk loop reads them from global memory. Carried across chunks (uniform in the
+// workgroup): total positive / negative weight, raw, and the open tie group's two sums -- a tie group may span
+// chunks; a row's neighbours are read directly, so no previous score is carried.
+template <bool PRE, bool AUC>
+__global__ __launch_bounds__(SR_THREADS) void seg_rank_block_kernel(SegRankArgs a, int npad_max) {
+  extern __shared__ double sr_lds[];              // !PRE: keys [npad_max], then local indices [npad_max]
+  __shared__ double w_gp[4], w_gn[4], w_P[4], w_N[4], w_raw[4];
+  __shared__ int w_f[4], w_hit[4];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const long long b = blockIdx.x;
+  if (b >= a.n_list) return;
+  const long long g = a.list[b];
+  if (g < 0 || g >= a.n_groups) return;
+  long long r0, L;
+  if (PRE) {
+    r0 = a.lptr[b];
+    L = a.lptr[b + 1] - r0;
+  } else {
+    r0 = a.seg_ptr[g];
+    L = a.seg_ptr[g + 1] - r0;
+  }
+  if (L < 1 || r0 < 0 || r0 + L > a.n_rows || (!PRE && L > npad_max)) {    // uniform in the workgroup
+    if (tid == 0) a.out[g] = (double)NAN;
+    return;
+  }
+  double* key = sr_lds;
+  int* ix = (int*)(sr_lds + npad_max);
+  if (!PRE) {
+    int npad = 64;
+    while (npad < L) npad <<= 1;                  // <= npad_max (a power of two >= L)
+    for (int i = tid; i < npad; i += SR_THREADS) {
+      double s = -INFINITY;
+      if (i < L) {
+        const long long pr = a.perm[r0 + i];
+        s = (pr >= 0 && pr < a.n_rows) ? a.scores[pr] : (double)NAN;
+        if (s != s) *a.nan_flag = 1;
+      }
+      key[i] = s;
+      ix[i] = i;
+    }
+    __syncthreads();
+    for (int k = 2; k <= npad; k <<= 1) {
+      for (int j = k >> 1; j > 0; j >>= 1) {
+        for (int t = tid; t < npad / 2; t += SR_THREADS) {
+          const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), q = i | j;
+          const bool up = (i & k) == 0;
+          const double si = key[i], sq = key[q];
+          const int ii = ix[i], iq = ix[q];
+          if (sr_before(si, ii, sq, iq) != up) {
+            key[i] = sq; key[q] = si;
+            ix[i] = iq; ix[q] = ii;
+          }
+        }
+        __syncthreads();
+      }
+    }
+  }
+  if (!AUC) {
+    const long long kk = a.k < L ? a.k : L;
+    int hit = 0;
+    for (long long pos = tid; pos < (PRE ? L : kk); pos += SR_THREADS) {
+      if (PRE) {
+        const double s = a.scores[r0 + pos];
+        if (s != s) *a.nan_flag = 1;
+        if (pos < kk) hit += a.flag[r0 + pos] != 0;
+      } else {
+        const int li = ix[pos];
+        if (li < L) hit += a.flag[r0 + li] != 0;  // a padding row can only come this far up after a NaN
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) hit += __shfl_xor(hit, o, 64);
+    if (lane == 0) w_hit[wv] = hit;
+    __syncthreads();
+    if (tid == 0) a.out[g] = (double)(w_hit[0] + w_hit[1] + w_hit[2] + w_hit[3]) / (double)a.k;
+    return;
+  }
+  double TP = 0.0, TN = 0.0, RAW = 0.0, ogp = 0.0, ogn = 0.0;
+  for (long long c0 = 0; c0 < L; c0 += SR_THREADS) {
+    const long long pos = c0 + tid;
+    const bool valid = pos < L;
+    double p = 0.0, n = 0.0;
+    bool f = false, tail = false;
+    if (valid) {
+      double s, sp = 0.0, sn = 0.0, w = 0.0;
+      bool fl = false;
+      if (PRE) {
+        s = a.scores[r0 + pos];
+        if (s != s) *a.nan_flag = 1;
+        if (pos > 0) sp = a.scores[r0 + pos - 1];
+        if (pos + 1 < L) sn = a.scores[r0 + pos + 1];
+        w = a.wts[r0 + pos];
+        fl = a.flag[r0 + pos] != 0;
+      } else {
+        s = key[pos];
+        if (pos > 0) sp = key[pos - 1];
+        if (pos + 1 < L) sn = key[pos + 1];
+        const int li = ix[pos];
+        if (li < L) {
+          w = a.wts[r0 + li];
+          fl = a.flag[r0 + li] != 0;
+        }
+      }
+      p = fl ? w : 0.0;
+      n = w - p;
+      f = pos == 0 || s != sp;
+      tail = pos == L - 1 || s != sn;
+    }
+    double gp = p, gn = n, P = p, N = n;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const double tgp = __shfl_up(gp, d, 64), tgn = __shfl_up(gn, d, 64), tP = __shfl_up(P, d, 64);
+      const int tf = __shfl_up((int)f, d, 64);
+      if (lane >= d) {
+        P += tP;
+        if (!f) { gp += tgp; gn += tgn; f = tf != 0; }
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) N += __shfl_xor(N, o, 64);
+    if (lane == 63) { w_f[wv] = f; w_gp[wv] = gp; w_gn[wv] = gn; w_P[wv] = P; w_N[wv] = N; }
+    __syncthreads();
+    double cp = ogp, cn = ogn, Pb = TP;           // what the waves (and chunks) before this one leave open
+    for (int v = 0; v < wv; ++v) {
+      if (w_f[v]) { cp = w_gp[v]; cn = w_gn[v]; } else { cp += w_gp[v]; cn += w_gn[v]; }
+      Pb += w_P[v];
+    }
+    if (!f) { gp += cp; gn += cn; }
+    P += Pb;
+    double raw = tail ? (P - gp) * gn + gp * gn / 2.0 : 0.0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) raw += __shfl_xor(raw, o, 64);
+    if (lane == 0) w_raw[wv] = raw;
+    __syncthreads();
+    for (int v = 0; v < 4; ++v) {
+      if (w_f[v]) { ogp = w_gp[v]; ogn = w_gn[v]; } else { ogp += w_gp[v]; ogn += w_gn[v]; }
+      TP += w_P[v];
+      TN += w_N[v];
+      RAW += w_raw[v];
+    }
+    __syncthreads();
+  }
+  if (tid == 0) a.out[g] = RAW / (TP * TN);
+}
+
 extern "C" {
 
 const char* pml_build_id() { return pml_build_stamp + 13; }
+
+// Per-group ranking metric of the groups a->list of one size class (cls 0: C16, 1: C64, 2: CWG, 3: LONG / pre-sorted)
+// into a->out; k = 0: AUC, k > 0: precision@k. npad_max (CWG): a power of two >= the longest listed group, <= 4096.
+int pml_seg_rank_eval(int cls, int k, const SegRankArgs* a, int npad_max, void* stream) {
+  if (a->n_list <= 0) return 0;
+  if (k < 0 || cls < 0 || cls > 3) return -22;
+  hipStream_t st = (hipStream_t)stream;
+  SegRankArgs v = *a;
+  v.k = k;
+  const long long per = cls == 0 ? SR_THREADS / 16 : cls == 1 ? SR_THREADS / 64 : 1;
+  const long long blocks = (v.n_list + per - 1) / per;
+  if (blocks > 0x7fffffffLL) return -22;
+  const dim3 grid((unsigned)blocks), blk(SR_THREADS);
+  if (cls == 0) {
+    if (k) hipLaunchKernelGGL((seg_rank_wave_kernel<16, false>), grid, blk, 0, st, v);
+    else hipLaunchKernelGGL((seg_rank_wave_kernel<16, true>), grid, blk, 0, st, v);
+  } else if (cls == 1) {
+    if (k) hipLaunchKernelGGL((seg_rank_wave_kernel<64, false>), grid, blk, 0, st, v);
+    else hipLaunchKernelGGL((seg_rank_wave_kernel<64, true>), grid, blk, 0, st, v);
+  } else if (cls == 2) {
+    if (npad_max < 64 || npad_max > SR_WG_MAX || (npad_max & (npad_max - 1))) return -22;
+    const size_t lds = (size_t)npad_max * (sizeof(double) + sizeof(int));
+    if (k) hipLaunchKernelGGL((seg_rank_block_kernel<false, false>), grid, blk, lds, st, v, npad_max);
+    else hipLaunchKernelGGL((seg_rank_block_kernel<false, true>), grid, blk, lds, st, v, npad_max);
+  } else {
+    if (k) hipLaunchKernelGGL((seg_rank_block_kernel<true, false>), grid, blk, 0, st, v, 0);
+    else hipLaunchKernelGGL((seg_rank_block_kernel<true, true>), grid, blk, 0, st, v, 0);
+  }
+  LAUNCH_CHECK();
+  return 0;
+}
 
 int pml_downsample(int f64, const void* y, const void* w0, const long long* rowid, long long n,
                    unsigned long long seed, double rate, int binary, void* w, void* stream) {

@@ -65,6 +65,14 @@ class CmpArgs(ctypes.Structure):
                 ("oval", c_void_p)]
 
 
+class SegRankArgs(ctypes.Structure):
+    """Arguments of the per-group ranking kernels (``seg_rank_*_kernel``, ops/csrc/game_kernels.hip)."""
+    _fields_ = [("seg_ptr", c_void_p), ("perm", c_void_p), ("scores", c_void_p), ("wts", c_void_p),
+                ("flag", c_void_p), ("list", c_void_p), ("lptr", c_void_p), ("out", c_void_p),
+                ("nan_flag", c_void_p), ("n_list", ctypes.c_longlong), ("n_rows", ctypes.c_longlong),
+                ("n_groups", ctypes.c_longlong), ("k", c_int)]
+
+
 class TLTDesc(ctypes.Structure):
     _fields_ = [
         ("items", c_void_p), ("nitems", c_int), ("cbits", c_int), ("pack", c_void_p), ("val", c_void_p),
@@ -699,6 +707,8 @@ def game_lib() -> Optional[ctypes.CDLL]:
         lib.pml_key_hist.restype = c_int
         lib.pml_tl_compact.argtypes = [c_int, c_int, ctypes.POINTER(CmpArgs), c_void_p]
         lib.pml_tl_compact.restype = c_int
+        lib.pml_seg_rank_eval.argtypes = [c_int, c_int, ctypes.POINTER(SegRankArgs), c_int, c_void_p]
+        lib.pml_seg_rank_eval.restype = c_int
         for f in ("pml_score_rows", "pml_gemm_nt", "pml_spmm_rows", "pml_downsample"):
             getattr(lib, f).restype = c_int
         lib._pml_typed = True
@@ -786,6 +796,101 @@ def csr_gather_rows(nip: torch.Tensor, pos: torch.Tensor, val: torch.Tensor, row
         optr.data_ptr(), None if cbase is None else cbase.data_ptr(), ocol.data_ptr(), oval.data_ptr(),
         stream_handle(dev)), "csr_gather_rows")
     return ocol, oval
+
+
+SEG_RANK_CLASSES = ("C16", "C64", "CWG", "LONG")
+SEG_RANK_WG_CAP = 4096
+
+
+def seg_rank_caps(wg_max: int) -> dict:
+    """Longest group every size class of the ranking kernels takes (LONG: unbounded)."""
+    return {"C16": min(16, wg_max), "C64": min(64, wg_max), "CWG": min(wg_max, SEG_RANK_WG_CAP), "LONG": None}
+
+
+def check_seg_rank_layout(lay, scores: torch.Tensor) -> None:
+    """Host-side validation of everything the ranking kernels index through (``PML_CHECK_KERNEL_INPUTS=1``)."""
+    n, ng = int(lay.n), int(lay.n_groups)
+    if scores.numel() != n or scores.dtype != torch.float64 or not scores.is_contiguous():
+        raise ValueError(f"seg_rank_eval: scores must be {n} contiguous fp64 values")
+    ptr = lay.seg_ptr.cpu().numpy()
+    if ptr.shape != (ng + 1,) or ptr[0] != 0 or ptr[-1] != n or np.any(np.diff(ptr) < 0):
+        raise ValueError("seg_rank_eval: seg_ptr must be non-decreasing from 0 to n")
+    perm = lay.perm.cpu().numpy()
+    if perm.shape != (n,) or (n and (perm.min() < 0 or perm.max() >= n)) \
+            or np.any(np.bincount(perm, minlength=n) != 1):
+        raise ValueError("seg_rank_eval: perm is not a permutation of [0, n)")
+    if lay.wts.numel() != n or lay.flag.numel() != n:
+        raise ValueError("seg_rank_eval: group-ordered weights / flags must hold n values")
+    lens = np.diff(ptr)
+    caps = seg_rank_caps(int(lay.wg_max))
+    seen = np.zeros(ng, dtype=np.int64)
+    for c in SEG_RANK_CLASSES:
+        lst = lay.lists[c].cpu().numpy()
+        if lst.size == 0:
+            continue
+        if lst.min() < 0 or lst.max() >= ng:
+            raise ValueError(f"seg_rank_eval: class {c} lists a group outside [0, {ng})")
+        ll = lens[lst]
+        if np.any(ll < 1) or (caps[c] is not None and np.any(ll > caps[c])):
+            raise ValueError(f"seg_rank_eval: class {c} lists a group whose length does not fit the class")
+        np.add.at(seen, lst, 1)
+    if np.any(seen != (lens > 0)):
+        raise ValueError("seg_rank_eval: every non-empty group must be listed in exactly one class")
+    if int(lay.cwg_pad) < 64 or int(lay.cwg_pad) > SEG_RANK_WG_CAP or int(lay.cwg_pad) & (int(lay.cwg_pad) - 1) \
+            or (lay.lists["CWG"].numel() and lens[lay.lists["CWG"].cpu().numpy()].max() > int(lay.cwg_pad)):
+        raise ValueError("seg_rank_eval: cwg_pad must be a power of two in [64, 4096] >= the longest CWG group")
+    lg = lay.lists["LONG"].cpu().numpy()
+    lp = np.concatenate([[0], np.cumsum(lens[lg])]).astype(np.int64)
+    rows = np.concatenate([np.arange(ptr[g], ptr[g + 1]) for g in lg]) if lg.size else np.zeros(0, np.int64)
+    gid = np.repeat(np.arange(lg.size), lens[lg])
+    if not (np.array_equal(lay.long_ptr.cpu().numpy(), lp) and np.array_equal(lay.long_rows.cpu().numpy(), rows)
+            and np.array_equal(lay.long_gid.cpu().numpy(), gid)):
+        raise ValueError("seg_rank_eval: LONG row tables do not match seg_ptr")
+
+
+def seg_rank_eval(lay, scores: torch.Tensor, k: int = 0) -> Optional[torch.Tensor]:
+    """Per-group ranking metric of ``scores`` (fp64, row order) over the group layout ``lay``
+    (:class:`~photon_ml_amd.evaluation.segmented.GroupedRanking`): weighted tie-grouped AUC (``k = 0``) or
+    precision@k, one fp64 value per group (NaN where undefined), from ``seg_rank_wave_kernel`` /
+    ``seg_rank_block_kernel`` -- one launch per populated size class. LONG groups (longer than ``lay.wg_max``) are
+    gathered and ordered here by two stable sorts (score descending, then group) and streamed by the pre-sorted
+    kernel. Returns None when a score is NaN (the caller falls back to the host loop). Deterministic."""
+    lib = require_game_lib()
+    if k < 0:
+        raise ValueError(f"seg_rank_eval: k must be >= 0: {k}")
+    if not (scores.is_cuda and lay.perm.is_cuda):
+        raise RuntimeError("seg_rank_eval needs the layout and the scores on a GPU")
+    if os.environ.get("PML_CHECK_KERNEL_INPUTS", "0") == "1":
+        check_seg_rank_layout(lay, scores)
+    assert scores.dtype == torch.float64 and scores.is_contiguous() and scores.numel() == lay.n
+    dev = scores.device
+    out = torch.full((max(lay.n_groups, 1),), float("nan"), dtype=torch.float64, device=dev)
+    nan_flag = torch.zeros(1, dtype=torch.int32, device=dev)
+    st = stream_handle(dev)
+    a = SegRankArgs(seg_ptr=lay.seg_ptr.data_ptr(), perm=lay.perm.data_ptr(), scores=scores.data_ptr(),
+                    wts=lay.wts.data_ptr(), flag=lay.flag.data_ptr(), lptr=None, out=out.data_ptr(),
+                    nan_flag=nan_flag.data_ptr(), n_rows=lay.n, n_groups=lay.n_groups, k=int(k))
+    for cls, name in enumerate(SEG_RANK_CLASSES[:3]):
+        lst = lay.lists[name]
+        if lst.numel():
+            a.list, a.n_list = lst.data_ptr(), lst.numel()
+            check(lib.pml_seg_rank_eval(cls, int(k), ctypes.byref(a), int(lay.cwg_pad), st), f"seg_rank_eval {name}")
+    lst = lay.lists["LONG"]
+    if lst.numel():
+        s = scores[lay.perm[lay.long_rows]] + 0.0            # -0.0 -> 0.0: the radix sort must see them tie
+        o1 = torch.sort(s, descending=True, stable=True).indices
+        o2 = torch.sort(lay.long_gid[o1], stable=True).indices
+        o = o1[o2]
+        ss, rows = s[o].contiguous(), lay.long_rows[o]
+        ws, fs = lay.wts[rows].contiguous(), lay.flag[rows].contiguous()
+        b = SegRankArgs(seg_ptr=None, perm=None, scores=ss.data_ptr(), wts=ws.data_ptr(), flag=fs.data_ptr(),
+                        list=lst.data_ptr(), lptr=lay.long_ptr.data_ptr(), out=out.data_ptr(),
+                        nan_flag=nan_flag.data_ptr(), n_list=lst.numel(), n_rows=ss.numel(),
+                        n_groups=lay.n_groups, k=int(k))
+        check(lib.pml_seg_rank_eval(3, int(k), ctypes.byref(b), 0, st), "seg_rank_eval LONG")
+    if int(nan_flag.item()):
+        return None
+    return out[:lay.n_groups]
 
 
 def sorted_counts(sorted_keys: torch.Tensor, nbins: int) -> torch.Tensor:
