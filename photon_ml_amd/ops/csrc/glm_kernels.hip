@@ -24,6 +24,7 @@
 #include <stdint.h>
 #include <math.h>
 #include <algorithm>
+#include <type_traits>
 
 #define NB 4096          // max entries per block
 #define NTHREADS 256     // 4 wave64 per block
@@ -1353,9 +1354,10 @@ struct TLTMultiDesc {
   const unsigned char* live_mt;
 };
 
-// Runtime TL configuration: accumulator precision for bf16/f32 data (0 = fp32 LDS, 1 = fp64 LDS) and the number
-// of waves per work-group (2 or 4: each wave owns an LDS accumulator row, so fewer waves = less LDS per WG = more
-// resident WGs per CU). fp64 data always accumulates in fp64.
+// Runtime TL configuration (pml_tl_config; read by the experiment build's launch ladder only, see TL_EXPERIMENT):
+// accumulator precision for bf16/f32 data (0 = fp32 LDS, 1 = fp64 LDS) and the number of waves per work-group (2 or
+// 4: each wave owns an LDS accumulator row, so fewer waves = less LDS per WG = more resident WGs per CU). fp64 data
+// always accumulates in fp64.
 static int g_ablate = 0;      // profiling ablation bits (0 in production)
 // FWD_LS arguments (set by pml_set_ls_args right before a direction pass; host-side, single stream)
 static double* g_ls_z0 = nullptr;
@@ -1368,6 +1370,29 @@ static inline A& with_ls_in(A& a) {
   a.z0_in = g_ls_z0_in ? g_ls_z0_in : g_ls_z0;
   a.zd_in = g_ls_zd_in ? g_ls_zd_in : a.z_out;
   return a;
+}
+// The forward entry points' epilogue arguments for vectors of type XT (the row-data pointers arrive untyped).
+// The ablation bits reach only the seg_* kernels through here: the tiled kernels read c_tl_ablate (TL_ABL).
+template <typename XT>
+static FwdArgs<XT, XT> fwd_args(int mode, int loss, double shift, const void* y, const void* off, const void* wt,
+                                void* coef, void* dzz, double* z_out, int with_offset) {
+  FwdArgs<XT, XT> a{mode, loss, shift, (const XT*)y, (const XT*)off, (const XT*)wt, (XT*)coef, (XT*)dzz, z_out,
+                    with_offset, g_ablate, 0, g_ls_z0, g_ls_t0, g_ls_tpend};
+  return with_ls_in(a);
+}
+// prec of the C entry points: 0 = bf16 values with fp32 vectors, 1 = fp32, 2 = fp64. f(VT{}, XT{}); with_prec_sq
+// adds the transposes' square flag as a third, bool_constant argument.
+template <typename F>
+static int with_prec(int prec, F f) {
+  if (prec == 2) return f(double{}, double{});
+  if (prec == 1) return f(float{}, float{});
+  return f(uint16_t{}, float{});
+}
+template <typename F>
+static int with_prec_sq(int prec, int square, F f) {
+  return with_prec(prec, [&](auto vt, auto xt) {
+    return square ? f(vt, xt, std::true_type{}) : f(vt, xt, std::false_type{});
+  });
 }
 static int g_tl_acc64 = 1;   // measured on MI355X: ds_add_f64 accumulation is ~3x faster than ds_add_f32 here
 static int g_tl_waves = 4;     // forward
@@ -1383,179 +1408,141 @@ static int g_rs_variant = 5;   // rs_tron variant: 0-2 rs_tron_kernel<V>; for n 
 static int g_tl_deep = 0;      // interleaved forward: 0 two-slot pipeline (P = 3), 1 deep S4/D1 (P = 5), 2 S6/D2 (P = 6)
 static int g_tl_deep_t = 0;    // interleaved transpose: same
 
-// Production builds compile only the production stream pipelines (interleaved layout: P = 3, plain: P = 0), the
-// production wave counts (forward 2, transpose 4) and fp64 LDS accumulation; the A/B variants behind the runtime
-// knobs (tl_pipe, tl_deep, tl_waves, tl_acc64) exist only in the experiment build (-DPML_TL_EXPERIMENT,
-// ops/build.py build_experiment, loaded with PML_GLM_LIB), where the knobs select them.
+// The production build instantiates only the kernels it can launch: the production stream pipelines (interleaved
+// layout: P = 3, plain: P = 0), the production wave counts (forward 2, transpose 4) and the accumulators of
+// tl_with_acc below. The A/B variants behind the runtime knobs (tl_pipe, tl_deep, tl_waves, tl_acc64) are
+// instantiated only in the experiment build (-DPML_TL_EXPERIMENT, ops/build.py build_experiment, loaded with
+// PML_GLM_LIB), where the knobs select them; production ignores the knobs. Every branch on this flag is an
+// `if constexpr` inside a template: a runtime `if` on a constant would still instantiate the kernel it guards.
 #ifdef PML_TL_EXPERIMENT
-#define TL_KNOB(x) (x)
-#define TL_WAVES_F g_tl_waves
-#define TL_WAVES_T g_tl_waves_t
+constexpr bool TL_EXPERIMENT = true;
 #else
-#define TL_KNOB(x) 0
-#define TL_WAVES_F 2
-#define TL_WAVES_T 4
+constexpr bool TL_EXPERIMENT = false;
 #endif
 
-// LDS accumulator type by block / tile width, the same for the per-chunk and the shard-wide entry points. Up to
-// 11 bits the accumulators are fp64 (always for fp64 data; bf16 / fp32 data: unless the experiment build's tl_acc64
-// knob is off). 4096 fp64 slots per wave do not fit the 64 KB of a work-group (transpose: 4 waves x 32 KB), so
-// width 12 exists for bf16 / fp32 data only and accumulates in fp32 (4 waves x 16 KB); fp64 data stop at 11 bits
-// (TL_MAXBITS_F64 in ops/tiled.py).
+template <typename AT_, int MAXR_> struct TLAcc { using AT = AT_; static constexpr int MAXR = MAXR_; };
+template <int NW_, int P_> struct TLPipe { static constexpr int NW = NW_, P = P_; };
+
+// LDS accumulator type and slot count by block / tile width, the one rule of all four entry points: f(TLAcc<AT,
+// MAXR>), or -22 for a width outside [1, tl_maxbits]. Up to 11 bits the accumulators are fp64 (always for fp64
+// data; bf16 / fp32 data: unless the experiment build's tl_acc64 knob is off). 4096 fp64 slots per wave do not fit
+// the 64 KB of a work-group (transpose: 4 waves x 32 KB), so width 12 exists for bf16 / fp32 data only and
+// accumulates in fp32 (4 waves x 16 KB); fp64 data stop at 11 bits (TL_MAXBITS_F64 in ops/tiled.py).
 template <typename XT> static inline int tl_maxbits() { return sizeof(XT) == 8 ? 11 : TL_MAXBITS; }
-template <typename XT> static inline bool tl_acc64(int bits) {
-  return sizeof(XT) == 8 || (bits <= 11 && !TL_KNOB(!g_tl_acc64));
+template <typename XT, typename F>
+static int tl_with_acc(int bits, F f) {
+  if (bits < 1 || bits > tl_maxbits<XT>()) return -22;
+  if constexpr (sizeof(XT) != 8) {
+    if (bits == 12) { f(TLAcc<float, 4096>{}); return 0; }
+    if constexpr (TL_EXPERIMENT) {
+      if (!g_tl_acc64) {
+        if (bits <= 10) f(TLAcc<float, 1024>{}); else f(TLAcc<float, 2048>{});
+        return 0;
+      }
+    }
+  }
+  if (bits <= 10) f(TLAcc<double, 1024>{}); else f(TLAcc<double, 2048>{});
+  return 0;
 }
 
-template <typename VT, typename XT, typename RT, typename AT, int MAXR>
-static void tl_fwd_launch(const TLFwdDesc* c, const void* x, FwdArgs<XT, RT> a, double* stats, hipStream_t st) {
-#define TLF(NW, P) hipLaunchKernelGGL((tl_fwd_kernel<VT, XT, RT, AT, MAXR, 2, NW, P>), dim3(c->nblk), dim3(NW * 64), 0, \
-                                    st, c->blk, c->rbits, c->pack, (const VT*)c->val, c->nar, (const XT*)x, a, stats, \
-                                    c->live)
-  if (c->il) {
-    if (TL_WAVES_F <= 2) { if (TL_KNOB(g_tl_deep) == 2) TLF(2, 6); else if (TL_KNOB(g_tl_deep)) TLF(2, 5); else TLF(2, 3); }
-    else { if (TL_KNOB(g_tl_deep) == 2) TLF(4, 6); else if (TL_KNOB(g_tl_deep)) TLF(4, 5); else TLF(4, 3); }
+// Waves per work-group and stream pipeline: f(TLPipe<NW, P>). Production: NW_PROD waves, P = 3 (interleaved
+// layout) or 0. Experiment build: waves 2, else 4 (pml_tl_config stores nothing else); interleaved: deep 0 / 1 / 2
+// -> P = 3 / 5 / 6; plain: pipe == ALT_P -> the entry point's alternative pipeline (per-chunk kernels: 1,
+// shard-wide kernels: 2), else 0.
+template <int NW_PROD, int ALT_P, typename F>
+static void tl_with_pipe(int il, int waves, int deep, int pipe, F f) {
+  if constexpr (!TL_EXPERIMENT) {
+    if (il) f(TLPipe<NW_PROD, 3>{}); else f(TLPipe<NW_PROD, 0>{});
+  } else {
+    auto with_p = [&](auto nw) {
+      constexpr int NW = decltype(nw)::value;
+      if (il) {
+        if (deep == 2) f(TLPipe<NW, 6>{}); else if (deep) f(TLPipe<NW, 5>{}); else f(TLPipe<NW, 3>{});
+      } else if (pipe == ALT_P) f(TLPipe<NW, ALT_P>{});
+      else f(TLPipe<NW, 0>{});
+    };
+    if (waves == 2) with_p(std::integral_constant<int, 2>{}); else with_p(std::integral_constant<int, 4>{});
   }
-  else if (TL_WAVES_F == 2) { if (TL_KNOB(g_tl_pipe) == 1) TLF(2, 1); else TLF(2, 0); }
-  else { if (TL_KNOB(g_tl_pipe) == 1) TLF(4, 1); else TLF(4, 0); }
-#undef TLF
 }
 
-template <typename VT, typename XT, typename RT, typename AT, int MAXR>
-static void tl_fwd_multi_launch(const TLFwdMultiDesc* c, const void* x, FwdArgs<XT, RT> a, double* stats,
-                                hipStream_t st) {
-#define TLM(NW, P) hipLaunchKernelGGL((tl_fwd_multi_kernel<VT, XT, RT, AT, MAXR, 2, NW, P>), dim3(c->nblk), \
-                                      dim3(NW * 64), 0, st, c->blk, c->rbits, c->ptrs, (const XT*)x, a, stats, \
-                                      c->live)
-  if (c->il) {
-    if (TL_KNOB(g_tl_deep) == 2) { if (TL_WAVES_F == 2) TLM(2, 6); else TLM(4, 6); }
-    else if (TL_KNOB(g_tl_deep)) { if (TL_WAVES_F == 2) TLM(2, 5); else TLM(4, 5); }
-    else { if (TL_WAVES_F == 2) TLM(2, 3); else TLM(4, 3); }
-  }
-  else if (TL_WAVES_F == 2) { if (TL_KNOB(g_tl_pipe) == 2) TLM(2, 2); else TLM(2, 0); }
-  else { if (TL_KNOB(g_tl_pipe) == 2) TLM(4, 2); else TLM(4, 0); }
-#undef TLM
+template <typename VT, typename XT, typename RT>
+static int tl_fwd_impl(const TLFwdDesc* c, const void* x, FwdArgs<XT, RT> a, double* stats, hipStream_t st) {
+  if (c->nblk <= 0) return 0;
+  const int rc = tl_with_acc<XT>(c->rbits, [&](auto acc) {
+    tl_with_pipe<2, 1>(c->il, g_tl_waves, g_tl_deep, g_tl_pipe, [&](auto pipe) {
+      using A = decltype(acc); using Q = decltype(pipe);
+      hipLaunchKernelGGL((tl_fwd_kernel<VT, XT, RT, typename A::AT, A::MAXR, 2, Q::NW, Q::P>), dim3(c->nblk),
+                         dim3(Q::NW * 64), 0, st, c->blk, c->rbits, c->pack, (const VT*)c->val, c->nar, (const XT*)x,
+                         a, stats, c->live);
+    });
+  });
+  if (rc) return rc;
+  LAUNCH_CHECK();
+  return 0;
 }
 
 template <typename VT, typename XT, typename RT>
 static int tl_fwd_multi_impl(const TLFwdMultiDesc* c, const void* x, FwdArgs<XT, RT> a, double* stats,
                              hipStream_t st) {
   if (c->nblk <= 0) return 0;
-  if (c->rbits < 1 || c->rbits > tl_maxbits<XT>()) return -22;
-  if (tl_acc64<XT>(c->rbits)) {
-    if (c->rbits <= 10) tl_fwd_multi_launch<VT, XT, RT, double, 1024>(c, x, a, stats, st);
-    else tl_fwd_multi_launch<VT, XT, RT, double, 2048>(c, x, a, stats, st);
-  } else if (c->rbits <= 10) {
-    tl_fwd_multi_launch<VT, XT, RT, float, 1024>(c, x, a, stats, st);
-  } else if (c->rbits == 11) {
-    tl_fwd_multi_launch<VT, XT, RT, float, 2048>(c, x, a, stats, st);
-  } else {
-    tl_fwd_multi_launch<VT, XT, RT, float, 4096>(c, x, a, stats, st);
-  }
+  const int rc = tl_with_acc<XT>(c->rbits, [&](auto acc) {
+    tl_with_pipe<2, 2>(c->il, g_tl_waves, g_tl_deep, g_tl_pipe, [&](auto pipe) {
+      using A = decltype(acc); using Q = decltype(pipe);
+      hipLaunchKernelGGL((tl_fwd_multi_kernel<VT, XT, RT, typename A::AT, A::MAXR, 2, Q::NW, Q::P>), dim3(c->nblk),
+                         dim3(Q::NW * 64), 0, st, c->blk, c->rbits, c->ptrs, (const XT*)x, a, stats, c->live);
+    });
+  });
+  if (rc) return rc;
   LAUNCH_CHECK();
   return 0;
 }
 
-template <typename VT, typename XT, typename RT>
-static int tl_fwd_impl(const TLFwdDesc* c, const void* x, FwdArgs<XT, RT> a, double* stats, hipStream_t st) {
-  if (c->nblk <= 0) return 0;
-  if (c->rbits < 1 || c->rbits > tl_maxbits<XT>()) return -22;
-  if (tl_acc64<XT>(c->rbits)) {
-    if (c->rbits <= 10) tl_fwd_launch<VT, XT, RT, double, 1024>(c, x, a, stats, st);
-    else tl_fwd_launch<VT, XT, RT, double, 2048>(c, x, a, stats, st);
-  } else if (c->rbits <= 10) {
-    tl_fwd_launch<VT, XT, RT, float, 1024>(c, x, a, stats, st);
-  } else if (c->rbits == 11) {
-    tl_fwd_launch<VT, XT, RT, float, 2048>(c, x, a, stats, st);
-  } else {
-    tl_fwd_launch<VT, XT, RT, float, 4096>(c, x, a, stats, st);
-  }
+// Level-1 / level-2 combine of the split tiles' partial rows (the level-1 rows follow the item partials in parts);
+// the same for the per-chunk and the shard-wide transpose descriptors.
+template <typename Desc>
+static int tl_t_combine(const Desc* c, double* G, double* parts, hipStream_t st) {
+  if (c->nmt <= 0) return 0;
+  const int C = 1 << c->cbits;
+  double* l1 = parts + (size_t)c->nparts_total * C;
+  hipLaunchKernelGGL(tl_t_combine1_kernel, dim3(c->ncu, (C + 63) / 64), dim3(NTHREADS), 0, st, c->cu, c->cbits,
+                     parts, l1, c->live_mt);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(tl_t_combine2_kernel, dim3(c->nmt, (C + 63) / 64), dim3(NTHREADS), 0, st,
+                     c->mt_tiles, c->mt_ptr, c->cbits, l1, G, c->dim, c->live_mt);
   LAUNCH_CHECK();
   return 0;
-}
-
-template <typename VT, typename XT, typename AT, bool SQ, int MAXR>
-static void tl_t_launch(const TLTDesc* c, const void* x, double* G, double* parts, hipStream_t st) {
-#define TLT(NW, P) hipLaunchKernelGGL((tl_t_kernel<VT, XT, AT, SQ, MAXR, 2, NW, P>), dim3(c->nitems), dim3(NW * 64), 0, \
-                                    st, c->items, c->cbits, c->pack, (const VT*)c->val, c->nar, (const XT*)x, G, c->dim, \
-                                    parts, c->live)
-  if (c->il) {
-    if (TL_WAVES_T == 2) { if (TL_KNOB(g_tl_deep_t) == 2) TLT(2, 6); else if (TL_KNOB(g_tl_deep_t)) TLT(2, 5); else TLT(2, 3); }
-    else { if (TL_KNOB(g_tl_deep_t) == 2) TLT(4, 6); else if (TL_KNOB(g_tl_deep_t)) TLT(4, 5); else TLT(4, 3); }
-  }
-  else if (TL_WAVES_T == 2) { if (TL_KNOB(g_tl_pipe_t) == 1) TLT(2, 1); else TLT(2, 0); }
-  else { if (TL_KNOB(g_tl_pipe_t) == 1) TLT(4, 1); else TLT(4, 0); }
-#undef TLT
 }
 
 template <typename VT, typename XT, bool SQ>
 static int tl_t_impl(const TLTDesc* c, const void* x, double* G, double* parts, hipStream_t st) {
   if (c->nitems <= 0) return 0;
-  if (c->cbits < 1 || c->cbits > tl_maxbits<XT>()) return -22;
-  if (tl_acc64<XT>(c->cbits)) {
-    if (c->cbits <= 10) tl_t_launch<VT, XT, double, SQ, 1024>(c, x, G, parts, st);
-    else tl_t_launch<VT, XT, double, SQ, 2048>(c, x, G, parts, st);
-  } else if (c->cbits <= 10) {
-    tl_t_launch<VT, XT, float, SQ, 1024>(c, x, G, parts, st);
-  } else if (c->cbits == 11) {
-    tl_t_launch<VT, XT, float, SQ, 2048>(c, x, G, parts, st);
-  } else {
-    tl_t_launch<VT, XT, float, SQ, 4096>(c, x, G, parts, st);
-  }
+  const int rc = tl_with_acc<XT>(c->cbits, [&](auto acc) {
+    tl_with_pipe<4, 1>(c->il, g_tl_waves_t, g_tl_deep_t, g_tl_pipe_t, [&](auto pipe) {
+      using A = decltype(acc); using Q = decltype(pipe);
+      hipLaunchKernelGGL((tl_t_kernel<VT, XT, typename A::AT, SQ, A::MAXR, 2, Q::NW, Q::P>), dim3(c->nitems),
+                         dim3(Q::NW * 64), 0, st, c->items, c->cbits, c->pack, (const VT*)c->val, c->nar, (const XT*)x,
+                         G, c->dim, parts, c->live);
+    });
+  });
+  if (rc) return rc;
   LAUNCH_CHECK();
-  if (c->nmt > 0) {
-    const int C = 1 << c->cbits;
-    double* l1 = parts + (size_t)c->nparts_total * C;
-    hipLaunchKernelGGL(tl_t_combine1_kernel, dim3(c->ncu, (C + 63) / 64), dim3(NTHREADS), 0, st, c->cu, c->cbits,
-                       parts, l1, c->live_mt);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(tl_t_combine2_kernel, dim3(c->nmt, (C + 63) / 64), dim3(NTHREADS), 0, st,
-                       c->mt_tiles, c->mt_ptr, c->cbits, l1, G, c->dim, c->live_mt);
-    LAUNCH_CHECK();
-  }
-  return 0;
-}
-
-template <typename VT, typename XT, typename AT, bool SQ, int MAXR>
-static void tl_t_multi_launch(const TLTMultiDesc* c, const void* x, double* G, double* parts, hipStream_t st) {
-#define TLTM(NW, P) hipLaunchKernelGGL((tl_t_multi_kernel<VT, XT, AT, SQ, MAXR, 2, NW, P>), dim3(c->nitems), \
-                                       dim3(NW * 64), 0, st, c->items, c->cbits, c->ptrs, (const XT*)x, G, \
-                                       c->dim, parts, c->live, g_gate)
-  if (c->il) {
-    if (TL_WAVES_T == 2) { if (TL_KNOB(g_tl_deep_t) == 2) TLTM(2, 6); else if (TL_KNOB(g_tl_deep_t)) TLTM(2, 5); else TLTM(2, 3); }
-    else { if (TL_KNOB(g_tl_deep_t) == 2) TLTM(4, 6); else if (TL_KNOB(g_tl_deep_t)) TLTM(4, 5); else TLTM(4, 3); }
-  }
-  else if (TL_WAVES_T == 2) { if (TL_KNOB(g_tl_pipe_t) == 2) TLTM(2, 2); else TLTM(2, 0); }
-  else { if (TL_KNOB(g_tl_pipe_t) == 2) TLTM(4, 2); else TLTM(4, 0); }
-#undef TLTM
+  return tl_t_combine(c, G, parts, st);
 }
 
 template <typename VT, typename XT, bool SQ>
 static int tl_t_multi_impl(const TLTMultiDesc* c, const void* x, double* G, double* parts, hipStream_t st) {
   if (c->nitems <= 0) return 0;
-  if (c->cbits < 1 || c->cbits > tl_maxbits<XT>()) return -22;
-  if (tl_acc64<XT>(c->cbits)) {
-    if (c->cbits <= 10) tl_t_multi_launch<VT, XT, double, SQ, 1024>(c, x, G, parts, st);
-    else tl_t_multi_launch<VT, XT, double, SQ, 2048>(c, x, G, parts, st);
-  } else if (c->cbits <= 10) {
-    tl_t_multi_launch<VT, XT, float, SQ, 1024>(c, x, G, parts, st);
-  } else if (c->cbits == 11) {
-    tl_t_multi_launch<VT, XT, float, SQ, 2048>(c, x, G, parts, st);
-  } else {
-    tl_t_multi_launch<VT, XT, float, SQ, 4096>(c, x, G, parts, st);
-  }
+  const int rc = tl_with_acc<XT>(c->cbits, [&](auto acc) {
+    tl_with_pipe<4, 2>(c->il, g_tl_waves_t, g_tl_deep_t, g_tl_pipe_t, [&](auto pipe) {
+      using A = decltype(acc); using Q = decltype(pipe);
+      hipLaunchKernelGGL((tl_t_multi_kernel<VT, XT, typename A::AT, SQ, A::MAXR, 2, Q::NW, Q::P>), dim3(c->nitems),
+                         dim3(Q::NW * 64), 0, st, c->items, c->cbits, c->ptrs, (const XT*)x, G, c->dim, parts, c->live,
+                         g_gate);
+    });
+  });
+  if (rc) return rc;
   LAUNCH_CHECK();
-  if (c->nmt > 0) {
-    const int C = 1 << c->cbits;
-    double* l1 = parts + (size_t)c->nparts_total * C;
-    hipLaunchKernelGGL(tl_t_combine1_kernel, dim3(c->ncu, (C + 63) / 64), dim3(NTHREADS), 0, st, c->cu, c->cbits,
-                       parts, l1, c->live_mt);
-    LAUNCH_CHECK();
-    hipLaunchKernelGGL(tl_t_combine2_kernel, dim3(c->nmt, (C + 63) / 64), dim3(NTHREADS), 0, st,
-                       c->mt_tiles, c->mt_ptr, c->cbits, l1, G, c->dim, c->live_mt);
-    LAUNCH_CHECK();
-  }
-  return 0;
+  return tl_t_combine(c, G, parts, st);
 }
 
 // ============================================================================================================
@@ -3715,33 +3702,20 @@ int pml_build_blocks(const int* seg_ptr, int nseg, int nb, int maxseg, int* blk,
 int pml_seg_fwd(int prec, const SegChunkDesc* c, const void* x, int mode, int loss, double shift,
                 const void* y, const void* off, const void* wt, void* coef, void* dzz, double* z_out,
                 int with_offset, double* stats, double* long_stats, double* parts, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (prec == 2) {
-    FwdArgs<double, double> a{mode, loss, shift, (const double*)y, (const double*)off, (const double*)wt,
-                              (double*)coef, (double*)dzz, z_out, with_offset, g_ablate, 0, g_ls_z0, g_ls_t0, g_ls_tpend};
-    return fwd_impl<double, double, double, double>(c, x, with_ls_in(a), stats, long_stats, parts, st);
-  }
-  FwdArgs<float, float> a{mode, loss, shift, (const float*)y, (const float*)off, (const float*)wt,
-                          (float*)coef, (float*)dzz, z_out, with_offset, g_ablate, 0, g_ls_z0, g_ls_t0, g_ls_tpend};
-  if (prec == 1) return fwd_impl<float, float, float, float>(c, x, with_ls_in(a), stats, long_stats, parts, st);
-  return fwd_impl<uint16_t, float, float, float>(c, x, with_ls_in(a), stats, long_stats, parts, st);
+  return with_prec(prec, [&](auto vt, auto xt) {
+    using VT = decltype(vt); using XT = decltype(xt);
+    return fwd_impl<VT, XT, XT, XT>(c, x, fwd_args<XT>(mode, loss, shift, y, off, wt, coef, dzz, z_out, with_offset),
+                                    stats, long_stats, parts, (hipStream_t)stream);
+  });
 }
-
 
 // Transpose pass over one CSC chunk: G[col] += sum val*x[row] (square=1: val^2). x is offset by caller so that
 // local row r of this chunk reads x[r].
 int pml_seg_t(int prec, const SegChunkDesc* c, const void* x, int square, double* G, double* parts, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (prec == 2) {
-    return square ? t_impl<double, double, double, true>(c, x, G, parts, st)
-                  : t_impl<double, double, double, false>(c, x, G, parts, st);
-  }
-  if (prec == 1) {
-    return square ? t_impl<float, float, float, true>(c, x, G, parts, st)
-                  : t_impl<float, float, float, false>(c, x, G, parts, st);
-  }
-  return square ? t_impl<uint16_t, float, float, true>(c, x, G, parts, st)
-                : t_impl<uint16_t, float, float, false>(c, x, G, parts, st);
+  return with_prec_sq(prec, square, [&](auto vt, auto xt, auto sq) {
+    using VT = decltype(vt); using XT = decltype(xt);
+    return t_impl<VT, XT, XT, decltype(sq)::value>(c, x, G, parts, (hipStream_t)stream);
+  });
 }
 
 // out[0..1] (+)= sum of n (F,S) pairs. scratch: >= 2*256 doubles. Deterministic for fixed n.
@@ -3764,45 +3738,45 @@ int pml_reduce_stats(const double* stats, int n, double* out, int accumulate, do
 
 // ---- tiled layout entry points ------------------------------------------------------------------------------
 int pml_tl_maxbits() { return TL_MAXBITS; }
-int pml_tl_experiment() { return TL_KNOB(1); }
+int pml_tl_experiment() { return TL_EXPERIMENT; }
+// Wave counts are 2 or 4: any other value (1 included, which the launch paths used to read each in its own way)
+// means 4. Only the experiment build's launch ladder reads these knobs.
 void pml_tl_config(int acc64, int waves, int waves_t, int pipe) {
-  g_tl_acc64 = acc64; g_tl_waves = (waves == 1 || waves == 2) ? waves : 4; g_tl_waves_t = waves_t == 2 ? 2 : 4; g_tl_pipe = pipe & 3; g_tl_pipe_t = (pipe >> 2) & 3;
+  g_tl_acc64 = acc64; g_tl_waves = waves == 2 ? 2 : 4; g_tl_waves_t = waves_t == 2 ? 2 : 4;
+  g_tl_pipe = pipe & 3; g_tl_pipe_t = (pipe >> 2) & 3;
 }
 
 int pml_tl_fwd(int prec, const TLFwdDesc* c, const void* x, int mode, int loss, double shift, const void* y,
                const void* off, const void* wt, void* coef, void* dzz, double* z_out, int with_offset,
                double* stats, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (prec == 2) {
-    FwdArgs<double, double> a{mode, loss, shift, (const double*)y, (const double*)off, (const double*)wt,
-                              (double*)coef, (double*)dzz, z_out, with_offset, g_ablate, 0, g_ls_z0, g_ls_t0, g_ls_tpend};
-    return tl_fwd_impl<double, double, double>(c, x, with_ls_in(a), stats, st);
-  }
-  FwdArgs<float, float> a{mode, loss, shift, (const float*)y, (const float*)off, (const float*)wt,
-                          (float*)coef, (float*)dzz, z_out, with_offset, g_ablate, 0, g_ls_z0, g_ls_t0, g_ls_tpend};
-  if (prec == 1) return tl_fwd_impl<float, float, float>(c, x, with_ls_in(a), stats, st);
-  return tl_fwd_impl<uint16_t, float, float>(c, x, with_ls_in(a), stats, st);
+  return with_prec(prec, [&](auto vt, auto xt) {
+    using VT = decltype(vt); using XT = decltype(xt);
+    return tl_fwd_impl<VT, XT, XT>(c, x, fwd_args<XT>(mode, loss, shift, y, off, wt, coef, dzz, z_out, with_offset),
+                                   stats, (hipStream_t)stream);
+  });
+}
+
+int pml_tl_fwd_multi(int prec, const TLFwdMultiDesc* c, const void* x, int mode, int loss, double shift,
+                     const void* y, const void* off, const void* wt, void* coef, void* dzz, double* z_out,
+                     int with_offset, double* stats, void* stream) {
+  return with_prec(prec, [&](auto vt, auto xt) {
+    using VT = decltype(vt); using XT = decltype(xt);
+    return tl_fwd_multi_impl<VT, XT, XT>(c, x, fwd_args<XT>(mode, loss, shift, y, off, wt, coef, dzz, z_out,
+                                                           with_offset), stats, (hipStream_t)stream);
+  });
 }
 
 int pml_tl_t(int prec, const TLTDesc* c, const void* x, int square, double* G, double* parts, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (prec == 2) return square ? tl_t_impl<double, double, true>(c, x, G, parts, st)
-                               : tl_t_impl<double, double, false>(c, x, G, parts, st);
-  if (prec == 1) return square ? tl_t_impl<float, float, true>(c, x, G, parts, st)
-                               : tl_t_impl<float, float, false>(c, x, G, parts, st);
-  return square ? tl_t_impl<uint16_t, float, true>(c, x, G, parts, st)
-                : tl_t_impl<uint16_t, float, false>(c, x, G, parts, st);
+  return with_prec_sq(prec, square, [&](auto vt, auto xt, auto sq) {
+    return tl_t_impl<decltype(vt), decltype(xt), decltype(sq)::value>(c, x, G, parts, (hipStream_t)stream);
+  });
 }
 
 int pml_tl_t_multi(int prec, const TLTMultiDesc* c, const void* x, int square, double* G, double* parts,
                    void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (prec == 2) return square ? tl_t_multi_impl<double, double, true>(c, x, G, parts, st)
-                               : tl_t_multi_impl<double, double, false>(c, x, G, parts, st);
-  if (prec == 1) return square ? tl_t_multi_impl<float, float, true>(c, x, G, parts, st)
-                               : tl_t_multi_impl<float, float, false>(c, x, G, parts, st);
-  return square ? tl_t_multi_impl<uint16_t, float, true>(c, x, G, parts, st)
-                : tl_t_multi_impl<uint16_t, float, false>(c, x, G, parts, st);
+  return with_prec_sq(prec, square, [&](auto vt, auto xt, auto sq) {
+    return tl_t_multi_impl<decltype(vt), decltype(xt), decltype(sq)::value>(c, x, G, parts, (hipStream_t)stream);
+  });
 }
 
 int pml_seg_cg_step(const long long* ptr, int nseg, double* step, double* r, double* d, const double* Hd,
@@ -4043,21 +4017,6 @@ int pml_segdot_long(const double* a, const double* b, int mode, const long long*
                      scratch, scratch + nch, out);
   LAUNCH_CHECK();
   return 0;
-}
-
-int pml_tl_fwd_multi(int prec, const TLFwdMultiDesc* c, const void* x, int mode, int loss, double shift,
-                     const void* y, const void* off, const void* wt, void* coef, void* dzz, double* z_out,
-                     int with_offset, double* stats, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (prec == 2) {
-    FwdArgs<double, double> a{mode, loss, shift, (const double*)y, (const double*)off, (const double*)wt,
-                              (double*)coef, (double*)dzz, z_out, with_offset, 0, 0, g_ls_z0, g_ls_t0, g_ls_tpend};
-    return tl_fwd_multi_impl<double, double, double>(c, x, with_ls_in(a), stats, st);
-  }
-  FwdArgs<float, float> a{mode, loss, shift, (const float*)y, (const float*)off, (const float*)wt,
-                          (float*)coef, (float*)dzz, z_out, with_offset, 0, 0, g_ls_z0, g_ls_t0, g_ls_tpend};
-  if (prec == 1) return tl_fwd_multi_impl<float, float, float>(c, x, with_ls_in(a), stats, st);
-  return tl_fwd_multi_impl<uint16_t, float, float>(c, x, with_ls_in(a), stats, st);
 }
 
 int pml_lds_add_order_probe(const double* v, double* out, int trials, hipStream_t st) {

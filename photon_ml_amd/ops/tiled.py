@@ -52,7 +52,7 @@ import torch
 
 from .native import TLFwdDesc, TLTDesc
 
-# Widths the kernels run (glm_kernels.hip tl_maxbits / tl_acc64), the same through the shard-wide launches
+# Widths the kernels run (glm_kernels.hip tl_maxbits / tl_with_acc), the same through the shard-wide launches
 # (tl_fwd_multi / tl_t_multi) and the per-chunk ones (tl_fwd / tl_t): 5 .. 11 bits for every precision with fp64 LDS
 # accumulators (4 waves x 2048 x 8 B = 64 KB at 11); 12 bits (4096 rows per block / columns per tile) for bf16 and
 # fp32 shards only, which accumulate in fp32 there (4 waves x 4096 x 4 B = 64 KB). An fp64 shard asking for 12 gets 11.
