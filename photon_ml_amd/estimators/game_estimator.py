@@ -199,11 +199,12 @@ class GameEstimator:
     def _validation_evaluators(self, validation: GameData):
         names = self.validation_evaluators or [default_validation_evaluator(self.training_task)]
         # per-group metrics (AUC:tag, PRECISION@k:tag) live on the training device: their kernels read the scores
-        # where score_rows_kernel wrote them; the simple evaluators keep their placement
+        # where score_rows_kernel wrote them; the simple evaluators keep their placement, except plain AUC under a
+        # process group on a GPU: its bucket exchange and count kernels run where the scores are
         dev = self.device if self.device is not None else default_device()
         types = [parse_evaluator_type(n) for n in names]
         return [build_evaluator(t, validation.response, validation.offsets, validation.weights, validation.id_tags,
-                                device=dev if t.is_multi else None) for t in types]
+                                device=dev if _evaluates_on(t, dev) else None) for t in types]
 
     def fit(self, data: GameData, validation: Optional[GameData],
             configurations: Sequence[Dict[str, GLMOptimizationConfiguration]]) -> List[GameResult]:
@@ -249,6 +250,14 @@ class GameEstimator:
         return results
 
 
+def _evaluates_on(etype, device) -> bool:
+    """Whether the evaluator ``etype`` is built on the scoring ``device``: the per-group metrics always, plain AUC
+    under a process group with a GPU device (single-process placement of the simple evaluators is unchanged)."""
+    if etype.is_multi:
+        return True
+    return (etype.name == "AUC" and device is not None and torch.device(device).type == "cuda" and is_dist())
+
+
 class GameTransformer:
     def __init__(self, model: GameModel, validation_evaluators: Optional[Sequence[str]] = None, device=None):
         """``device`` defaults to the current GPU (the HIP scoring kernels, K5/K6) and to the CPU without one."""
@@ -261,14 +270,15 @@ class GameTransformer:
         return self._evaluate(data, self.model.score(data, self.device), self.device)
 
     def _evaluate(self, data: GameData, scores, multi_device=None):
-        """``multi_device``: where the per-group evaluators live (None: with the labels, on the host)."""
+        """``multi_device``: where the per-group evaluators (and, under a process group on a GPU, plain AUC) live
+        (None: with the labels, on the host)."""
         evals = None
         if self.validation_evaluators:
             evals = []
             for n in self.validation_evaluators:
                 t = parse_evaluator_type(n)
                 e = build_evaluator(t, data.response, data.offsets, data.weights, data.id_tags,
-                                    device=multi_device if t.is_multi else None)
+                                    device=multi_device if _evaluates_on(t, multi_device) else None)
                 evals.append((e, e.evaluate(scores)))
         return scores, evals
 

@@ -12,8 +12,16 @@ Reference: ``photon-lib/.../evaluation/{Evaluator,EvaluatorType}.scala`` (evalua
   * name parsing ``AUC``, ``RMSE``, ``LOGISTIC_LOSS``, ..., ``PRECISION@5:queryId``, ``AUC:userId``.
 
 Sorting-based metrics run on the device (torch sort / segmented reductions), so the whole validation pass stays
-in HBM; the per-group metrics of a single-process GPU run are HIP kernels over a group layout built once
-(``segmented.py``), under a process group they gather their columns through the host.
+in HBM; the per-group metrics of a GPU run are HIP kernels over a group layout built once (``segmented.py``).
+
+Under a process group no metric gathers rows:
+  * ``AUC:tag`` / ``PRECISION@k:tag`` route every row once to the rank that owns its group
+    (``parallel/sharding.py``: ``entity_keys`` -> ``EntityPartitioner`` -> ``RowRouter``), an evaluation routes the
+    scores (one all-to-all of 8 B per row, device to device under RCCL), evaluates the owned groups locally and
+    all-reduces (sum, count) of the finite values (SURVEY C18);
+  * plain ``AUC`` is :func:`auc_distributed`: local sort, regular sampling, one all-to-all of score
+    buckets, integer counts per bucket (``ops/native.py::auc_counts``), a three-integer all-gather. Only when a
+    score is NaN do all ranks take the old gather path together.
 """
 from __future__ import annotations
 
@@ -84,10 +92,95 @@ def _gather(t: torch.Tensor) -> torch.Tensor:
     return torch.cat([x.to(t.device) for x in all_gather_varlen(t.detach().cpu())])
 
 
+AUC_SAMPLES = 64      # regular samples per rank that place the score-bucket splitters of auc_distributed
+
+
+def _gather_fixed(t: torch.Tensor) -> torch.Tensor:
+    """All-gather equally long small 1-D tensors; [world, len] on the host."""
+    import torch.distributed as dist
+    from ..parallel.dist import world_size
+    from ..parallel.sharding import comm_device
+    dev = comm_device()
+    t = t.to(dev)
+    outs = [torch.empty_like(t) for _ in range(world_size())]
+    dist.all_gather(outs, t)
+    return torch.stack(outs).cpu()
+
+
+def auc_distributed(scores: torch.Tensor, flags: torch.Tensor, info: Optional[dict] = None) -> float:
+    """Exact unweighted AUC of the rows of ALL ranks without gathering them; every rank passes its
+    shard's ``scores`` (fp64) and positive ``flags`` (uint8) and gets the same value, bitwise the value
+    ``auc_weighted`` gives on the concatenated rows while ``P N < 2^53``.
+
+    1. ``scores + 0.0`` (so -0.0 ties with 0.0 in the radix sort), sorted descending locally.
+    2. ``AUC_SAMPLES`` regular samples per rank and a NaN flag, one small all-gather; the sorted samples give
+       ``world - 1`` splitters. If any rank saw a NaN, every rank takes the gather path (``auc_weighted`` on all
+       rows): a collective decision.
+    3. The bucket of a row is the number of splitters strictly greater than its score -- a function of the value, so
+       a tie group never straddles ranks; buckets are contiguous in the sorted shard. One all-to-all each for the
+       scores and the flags (``RowRouter.exchange``).
+    4. The receiver sorts its bucket (segments of several ranks) and counts ``(2 raw, P, N)`` as integers (``auc_counts``: HIP on a GPU).
+    5. The three integers of every rank are all-gathered and combined in Python ints: bucket b adds
+       ``2 raw_b + 2 P_before_b N_b`` (``P_before_b``: positives of the higher-score buckets).
+
+    ``info`` (optional dict) receives ``path`` ("buckets" / "gather") and ``bucket_rows`` (rows received here)."""
+    from ..ops.native import auc_counts
+    from ..parallel.dist import world_size
+    from ..parallel.sharding import RowRouter
+    P = world_size()
+    s = _t(scores) + 0.0
+    dev = s.device
+    f = torch.as_tensor(flags, device=dev).to(torch.uint8)
+    n = int(s.numel())
+    s0, f0 = s, f                                           # row order, for the gather path
+    s, order = torch.sort(s, descending=True)
+    f = f[order]
+    S = AUC_SAMPLES
+    head = torch.zeros(2 + S, dtype=torch.float64, device=dev)
+    if n:
+        pos = (2 * torch.arange(S, dtype=torch.int64, device=dev) + 1) * n // (2 * S)
+        head[0] = 1.0
+        head[1] = torch.isnan(s).any().to(torch.float64)
+        head[2:] = s[pos]
+    got = _gather_fixed(head).numpy()
+    if info is not None:
+        info.update(path="buckets", bucket_rows=0)
+    if np.any(got[:, 1] != 0.0):
+        if info is not None:
+            info["path"] = "gather"
+        return auc_weighted(_gather(s0), _gather(f0.to(torch.float64)), None)
+    samples = np.sort(got[got[:, 0] != 0.0, 2:].ravel())[::-1]
+    if samples.size == 0:                                  # no rank holds a row
+        return float("nan")
+    split = torch.from_numpy(np.ascontiguousarray(samples[[k * samples.size // P for k in range(1, P)]])).to(dev)
+    # rows of bucket <= k: those with score >= split[k] (the shard is descending: search its negation)
+    ends = torch.searchsorted(-s, -split, right=True).tolist()
+    bounds = [0] + ends + [n]
+    router = RowRouter.from_counts([bounds[k + 1] - bounds[k] for k in range(P)])
+    rs, rf = router.exchange(s), router.exchange(f)
+    if info is not None:
+        info["bucket_rows"] = int(rs.numel())
+    if sum(1 for c in router.recv_counts if c) > 1:         # segments of several ranks: merge them by a sort
+        rs, o = torch.sort(rs, descending=True)
+        rf = rf[o]
+    counts = auc_counts(rs.contiguous(), rf.contiguous())
+    allc = _gather_fixed(counts).tolist()
+    tot2 = tp = tn = 0
+    for raw2, pb, nb in allc:                               # bucket 0 holds the highest scores
+        tot2 += int(raw2) + 2 * tp * int(nb)
+        tp += int(pb)
+        tn += int(nb)
+    if tp + tn >= 1 << 31:
+        raise ValueError(f"auc_distributed: {tp + tn} rows; the integer counts are kept below 2^31 rows")
+    if tp == 0 or tn == 0:
+        return float("nan")
+    return (tot2 / 2.0) / (float(tp) * float(tn))
+
+
 class Evaluator:
     """Evaluates ``scores + offsets`` against the labels. Under a process group every rank holds a row shard:
-    additive metrics (losses, RMSE) all-reduce their sums, rank metrics (AUC, per-group metrics) all-gather the
-    (score, label[, weight, group]) columns first."""
+    additive metrics (losses, RMSE) all-reduce their sums, plain AUC exchanges score buckets and the
+    per-group metrics route their rows to the groups' owners (C18); no metric gathers rows."""
 
     name = "EVALUATOR"
     higher_is_better = True
@@ -118,9 +211,15 @@ class Evaluator:
 class AUCEvaluator(Evaluator):
     name = "AUC"
 
+    def __init__(self, labels, offsets=None, weights=None, device=None):
+        super().__init__(labels, offsets, weights, device)
+        self.last_info: dict = {}
+        if self.distributed:
+            self.flags = (self.labels > POSITIVE_RESPONSE_THRESHOLD).to(torch.uint8)
+
     def _evaluate(self, s):
         if self.distributed:
-            return auc_weighted(_gather(s), _gather(self.labels), None)
+            return auc_distributed(s, self.flags, self.last_info)
         return auc_weighted(s, self.labels, None)  # MLlib AUC ignores weights
 
 
@@ -184,29 +283,42 @@ class SmoothedHingeLossEvaluator(_LossEvaluator):
 
 
 class MultiEvaluator(Evaluator):
-    """Per-group local metric, mean over groups whose value is finite."""
+    """Per-group local metric, mean over groups whose value is finite.
+
+    Under a process group a group's rows can sit on several ranks, so every row is routed ONCE, at construction,
+    to the rank that owns its group (the 64-bit ``entity_keys`` of the ids, one ``EntityPartitioner`` and one
+    ``RowRouter``); labels and weights travel with it. An evaluation routes ``scores + offsets`` (one all-to-all),
+    evaluates the owned groups here and all-reduces (sum, count) of the finite values. Routed rows arrive ordered
+    by source rank, then local position -- the order of the concatenation rank 0, rank 1, ... -- so ties at
+    position k of precision@k resolve as on the concatenated rows. Every rank issues the same collectives in the
+    same order whatever path it took locally (``last_path``)."""
 
     def __init__(self, ids, labels, offsets=None, weights=None, device=None):
         super().__init__(labels, offsets, weights, device)
         ids = np.asarray(ids)
-        if self.distributed:  # groups can span ranks: gather group keys once, evaluate on the gathered columns
-            from ..parallel.sharding import stable_hash64
-            keys = _gather(torch.from_numpy(stable_hash64(ids))).numpy()
-            uniq, inv = np.unique(keys, return_inverse=True)
-            self.labels_all = _gather(self.labels)
-            self.weights_all = _gather(self.weights)
+        dev = self.labels.device
+        self.router = None
+        if self.distributed:
+            from ..parallel.sharding import EntityPartitioner, RowRouter, entity_keys
+            keys = entity_keys(ids, dev)
+            self.router = RowRouter(EntityPartitioner.build_t(keys).owner_t(keys))
+            # the group layout below is over the rows this rank OWNS
+            self._y, self._w = self.router.forward(self.labels), self.router.forward(self.weights)
+            uniq, inv = torch.unique(self.router.forward(keys), sorted=True, return_inverse=True)
+            self.group = inv.to(torch.int64)
+            uniq = uniq.cpu().numpy()
         else:
             uniq, inv = np.unique(ids.astype(str) if ids.dtype == object else ids, return_inverse=True)
-        self.group = torch.as_tensor(inv, dtype=torch.int64, device=self.labels.device)
+            self.group = torch.as_tensor(inv, dtype=torch.int64, device=dev)
+            self._y, self._w = self.labels, self.weights
         self.n_groups = len(uniq)
         self.group_keys = uniq
         self.last_path = "host"
-        # single-process GPU runs evaluate every group in HIP kernels over a layout built once (K12); under a
-        # process group the columns are gathered through the host and evaluated by the loop below
+        # GPU runs evaluate every group in HIP kernels over a layout built once (K12)
         self.ranking = None
-        if self.labels.is_cuda and not self.distributed:
+        if self.labels.is_cuda:
             from .segmented import GroupedRanking
-            self.ranking = GroupedRanking(self.group, self.labels, self.weights, self.labels.device)
+            self.ranking = GroupedRanking(self.group, self._y, self._w, dev)
 
     def _local(self, s, y, w) -> float:
         raise NotImplementedError
@@ -217,20 +329,32 @@ class MultiEvaluator(Evaluator):
 
     def _values(self, s):
         """The metric of every group, NaN where it is undefined: an fp64 device tensor from the HIP kernels
-        (``last_path == "device"``) or a list of floats from the host loop (``"host"``)."""
+        (``last_path == "device"``) or a list of floats from the host loop (``"host"``). Under a process group:
+        of every group this rank owns, from the routed scores."""
+        if self.router is not None:
+            s = self.router.forward(s)
         vals = self._device_values(s) if self.ranking is not None else None
         self.last_path = "host" if vals is None else "device"
         return self._host_values(s) if vals is None else vals
 
     def evaluate_groups(self, scores):
-        """``(group_keys, values)``: the sorted distinct group ids (their stable hashes under a process group, where
-        every rank must call this) and the local metric of every group for ``scores + offsets`` as an fp64 tensor
-        on the evaluator's device, NaN where it is undefined."""
+        """``(group_keys, values)``: the sorted distinct group ids and the local metric of every group for
+        ``scores + offsets`` as an fp64 tensor on the evaluator's device, NaN where it is undefined. Under a process
+        group every rank must call this (the scores are routed) and gets the groups it OWNS, keyed by their stable
+        64-bit hashes: the ranks' key sets are disjoint and their union is every group."""
         vals = self._values(_t(scores, self.labels.device) + self.offsets)
         return self.group_keys, torch.as_tensor(vals, dtype=torch.float64, device=self.labels.device)
 
     def _evaluate(self, s):
         vals = self._values(s)
+        if self.distributed:
+            if self.last_path == "device":
+                tot, cnt = self.ranking.finite_sums(vals).tolist()
+            else:
+                vals = [v for v in vals if math.isfinite(v)]
+                tot, cnt = float(np.sum(vals)) if vals else 0.0, float(len(vals))
+            tot, cnt = _allsum(tot, cnt)
+            return tot / cnt if cnt > 0 else float("nan")
         if self.last_path == "device":
             return self.ranking.mean_finite(vals)
         vals = [v for v in vals if math.isfinite(v)]
@@ -239,10 +363,7 @@ class MultiEvaluator(Evaluator):
     def _host_values(self, s) -> List[float]:
         order = torch.argsort(self.group, stable=True)
         g = self.group[order]
-        if self.distributed:
-            s, y, w = _gather(s)[order], self.labels_all[order], self.weights_all[order]
-        else:
-            s, y, w = s[order], self.labels[order], self.weights[order]
+        s, y, w = s[order], self._y[order], self._w[order]
         counts = torch.bincount(g, minlength=self.n_groups).cpu().numpy()
         starts = np.concatenate([[0], np.cumsum(counts)])
         vals = [float("nan")] * self.n_groups

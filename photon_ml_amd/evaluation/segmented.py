@@ -15,8 +15,9 @@ LONG    > ``wg_max``         rows pre-sorted by two stable torch sorts, streamed
 ======  ===================  ==========================================================================
 
 A class takes no group longer than ``wg_max``, so a small ``wg_max`` pushes small groups through LONG
-(``wg_max = 0``: every group). The layout knows nothing about where its rows came from: a later owner-routed
-multi-rank evaluator only has to hand it the routed rows' group codes, labels and weights.
+(``wg_max = 0``: every group). The layout knows nothing about where its rows came from: under a process group
+``MultiEvaluator`` routes every row to the rank that owns its group and hands the layout the routed rows' group
+codes, labels and weights (a rank that owns nothing builds the empty layout, ``n = 0``).
 
 Reference: ``photon-api/.../evaluation/MultiEvaluator.scala:49-64``, ``AreaUnderROCCurveLocalEvaluator.scala:33-70``,
 ``PrecisionAtKLocalEvaluator.scala:39-51``.
@@ -104,9 +105,14 @@ class GroupedRanking:
         return self._eval(scores, int(k))
 
     @staticmethod
-    def mean_finite(values: torch.Tensor) -> float:
-        """Mean over the finite entries (one device reduction, one readback); NaN when there are none."""
+    def finite_sums(values: torch.Tensor) -> torch.Tensor:
+        """(sum, count) of the finite entries as two fp64 on the host (one device reduction, one readback)."""
         ok = torch.isfinite(values)
         tot = torch.where(ok, values, torch.zeros_like(values)).sum()
-        r = torch.stack([tot, ok.sum().to(torch.float64)]).cpu()
+        return torch.stack([tot, ok.sum().to(torch.float64)]).cpu()
+
+    @staticmethod
+    def mean_finite(values: torch.Tensor) -> float:
+        """Mean over the finite entries (one device reduction, one readback); NaN when there are none."""
+        r = GroupedRanking.finite_sums(values)
         return float(r[0] / r[1]) if float(r[1]) > 0 else float("nan")

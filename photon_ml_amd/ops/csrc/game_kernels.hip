@@ -13,6 +13,8 @@
 // * downsample_kernel — K20 fixed-effect down-sampling as an on-device weight rewrite.
 // * seg_rank_wave_kernel / seg_rank_block_kernel — K12 per-group AUC and precision@k (AUC:tag, PRECISION@k:tag):
 //   every group sorted in registers / LDS and evaluated in one pass, one launch per size class.
+// * auc_count_kernel / auc_count_combine_kernel -- integer tie-group counts of the global AUC over one sorted score
+//   stream (plain AUC under a process group: every rank counts the score bucket it received).
 //
 // Built with: hipcc --offload-arch=gfx950 -O3 -shared -fPIC (photon_ml_amd/ops/build.py). C ABI, ctypes.
 
@@ -562,6 +564,9 @@ __global__ __launch_bounds__(256) void csr_gather_rows_kernel(const long long* _
 // every launch gives the same bits. A NaN score sets *nan_flag (all writers store 1) and the wrapper discards the
 // result; the compare-exchange evaluates ONE predicate per pair on both sides, so even then the indices stay a
 // permutation and nothing is read out of bounds.
+// Under a process group every rank runs these kernels over the rows it OWNS: MultiEvaluator routes each row once to
+// the owner of its group and hands GroupedRanking the routed rows (n_list = 0 launches nothing: a rank may own no
+// group). The global AUC of all rows is not a per-group metric: see auc_count_kernel below.
 // ---------------------------------------------------------------------------------------------------------------
 struct SegRankArgs {
   const long long* seg_ptr;     // [n_groups + 1] (unused by the pre-sorted kernel)
@@ -806,9 +811,296 @@ __global__ __launch_bounds__(SR_THREADS) void seg_rank_block_kernel(SegRankArgs 
   if (tid == 0) a.out[g] = RAW / (TP * TN);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Global unweighted AUC counts of ONE sorted score stream (plain AUC under a process group: every rank evaluates the
+// score bucket it received, evaluation/evaluators.py::auc_distributed). Input: n scores sorted non-increasing and n
+// positive flags. Output, all int64: out[0] = sum over negative rows of (positives with a greater score) +
+// (positives with a greater or equal score) = 2 * sum_tiegroups (P_before gn + gp gn / 2), out[1] = positives,
+// out[2] = negatives. Tie test ==. Every sum is an integer, so the result does not depend on any order: no float
+// atomics, no atomics at all.
+//   auc_count_kernel: one workgroup per run of AC_ROWS rows, 16 contiguous rows per thread (eight 16-byte score
+//     loads and one 16-byte flag load). Rows are sorted, so the rows equal to the run's first / last score are exactly
+//     its leading / trailing tie group, which may continue in the neighbouring runs; every other ("interior") tie group
+//     closes here. For an interior negative row the two positive counts are the run-local prefix at its tie group's
+//     start (exclusive) and end (inclusive); they reach a thread whose rows do not hold that start / end by a
+//     last-valid max-scan and a first-valid min-scan over the threads. Summary per run (AC_SUMMARY int64 slots):
+//     first and last score, positives / negatives of the leading and the trailing group, totals, the interior sum
+//     and the interior negatives.
+//   auc_count_combine_kernel: one workgroup, one thread per run: adds 2 * P_before * (interior negatives) per run and
+//     closes the tie groups that span runs with prefix sums and running maxima over the runs (see the kernel).
+// Range: n < 2^31 keeps P * N < 2^62 and every term in int64.
+// ---------------------------------------------------------------------------------------------------------------
+#define AC_THREADS 256
+#define AC_T 16
+#define AC_ROWS (AC_THREADS * AC_T)
+#define AC_SUMMARY 10
+#define AC_CTHREADS 512               // threads (= runs per round) of the combine workgroup
+
+struct AucCountArgs {
+  const double* scores;         // [n] sorted non-increasing, 16-byte aligned
+  const unsigned char* flag;    // [n] positive flags, 16-byte aligned
+  long long* summ;              // [n_blocks * AC_SUMMARY] workspace
+  long long* out;               // [3]
+  long long n, n_blocks;
+};
+
+__device__ __forceinline__ long long ac_block_sum(long long v, long long* red, int lane, int wv) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();
+  if (lane == 0) red[wv] = v;
+  __syncthreads();
+  return red[0] + red[1] + red[2] + red[3];
+}
+
+__global__ __launch_bounds__(AC_THREADS) void auc_count_kernel(AucCountArgs a) {
+  __shared__ double t_first[AC_THREADS], t_last[AC_THREADS];
+  __shared__ long long red[4], w_cnt[4], w_s[4], w_e[4];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const long long r0 = (long long)blockIdx.x * AC_ROWS;
+  if (r0 >= a.n) return;                                      // uniform: never with the launcher's grid
+  const int nb = (int)((a.n - r0) < (long long)AC_ROWS ? (a.n - r0) : (long long)AC_ROWS);
+  const int t0 = tid * AC_T;
+  const int v = nb - t0 >= AC_T ? AC_T : (nb - t0 > 0 ? nb - t0 : 0);      // valid rows of this thread
+  double s[AC_T];
+  unsigned f = 0;                                             // bit j: row j is positive
+  if (v == AC_T) {
+    const double2* ps = reinterpret_cast<const double2*>(a.scores + r0 + t0);
+#pragma unroll
+    for (int j = 0; j < AC_T / 2; ++j) {
+      const double2 d = ps[j];
+      s[2 * j] = d.x;
+      s[2 * j + 1] = d.y;
+    }
+    const uint4 q = *reinterpret_cast<const uint4*>(a.flag + r0 + t0);
+    const unsigned qw[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int j = 0; j < AC_T; ++j) f |= (((qw[j >> 2] >> (8 * (j & 3))) & 0xffu) != 0u ? 1u : 0u) << j;
+  } else {
+#pragma unroll
+    for (int j = 0; j < AC_T; ++j) {
+      s[j] = 0.0;
+      if (j < v) {
+        s[j] = a.scores[r0 + t0 + j];
+        f |= (a.flag[r0 + t0 + j] != 0 ? 1u : 0u) << j;
+      }
+    }
+  }
+  double sl = s[0];                                           // this thread's last valid score
+#pragma unroll
+  for (int j = 1; j < AC_T; ++j) sl = j < v ? s[j] : sl;
+  t_first[tid] = s[0];
+  t_last[tid] = sl;
+  // run-local exclusive prefix of the positives over the threads
+  const int pc = __popc(f);
+  int inc = pc;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int t = __shfl_up(inc, d, 64);
+    if (lane >= d) inc += t;
+  }
+  if (lane == 63) w_cnt[wv] = inc;
+  __syncthreads();
+  int base = inc - pc, tot_p = 0;
+  for (int w = 0; w < 4; ++w) {
+    if (w < wv) base += (int)w_cnt[w];
+    tot_p += (int)w_cnt[w];
+  }
+  const double bfirst = t_first[0], blast = t_last[(nb - 1) / AC_T];
+  const double s_prev = t_last[tid > 0 ? tid - 1 : 0], s_next = t_first[tid < AC_THREADS - 1 ? tid + 1 : tid];
+  // tie-group starts / ends among this thread's rows: positives before its LAST start, positives through its FIRST end
+  unsigned st = 0, en = 0;
+#pragma unroll
+  for (int j = 0; j < AC_T; ++j) {
+    if (j < v) {
+      const bool sj = j == 0 ? (tid == 0 || s[0] != s_prev) : s[j] != s[j - 1];
+      const double nx = j == v - 1 ? s_next : s[(j + 1) % AC_T];          // j == AC_T - 1 implies j == v - 1
+      const bool ej = t0 + j == nb - 1 || s[j] != nx;
+      st |= (sj ? 1u : 0u) << j;
+      en |= (ej ? 1u : 0u) << j;
+    }
+  }
+  long long ks = 0, ke = 0x7fffffffffffffffLL;
+  if (st) {
+    const int j = 31 - __clz((int)st);
+    ks = ((long long)(tid + 1) << 32) | (long long)(base + __popc(f & ((1u << j) - 1u)));
+  }
+  if (en) {
+    const int j = __ffs((int)en) - 1;
+    ke = ((long long)tid << 32) | (long long)(base + __popc(f & ((2u << j) - 1u)));
+  }
+  long long xs = ks, xe = ke;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const long long ts = __shfl_up(xs, d, 64), te = __shfl_down(xe, d, 64);
+    if (lane >= d && ts > xs) xs = ts;
+    if (lane + d < 64 && te < xe) xe = te;
+  }
+  if (lane == 63) w_s[wv] = xs;
+  if (lane == 0) w_e[wv] = xe;
+  long long cl = __shfl_up(xs, 1, 64), cr = __shfl_down(xe, 1, 64);
+  if (lane == 0) cl = 0;
+  if (lane == 63) cr = 0x7fffffffffffffffLL;
+  __syncthreads();
+  for (int w = 0; w < 4; ++w) {
+    if (w < wv && w_s[w] > cl) cl = w_s[w];
+    if (w > wv && w_e[w] < cr) cr = w_e[w];
+  }
+  // interior negatives: positives strictly before their tie group (forward) + through its end (backward)
+  long long acc = 0;
+  int lead_p = 0, lead_n = 0, trail_p = 0, trail_n = 0, int_n = 0;
+  int cur = (int)(cl & 0xffffffffLL), cp = base;
+#pragma unroll
+  for (int j = 0; j < AC_T; ++j) {
+    if (j < v) {
+      const bool pos = (f >> j) & 1u, lead = s[j] == bfirst, trail = s[j] == blast;
+      if ((st >> j) & 1u) cur = cp;
+      if (!pos && !lead && !trail) { acc += cur; ++int_n; }
+      lead_p += lead && pos;
+      lead_n += lead && !pos;
+      trail_p += trail && pos;
+      trail_n += trail && !pos;
+      cp += pos;
+    }
+  }
+  cur = (int)(cr & 0xffffffffLL);                              // cp = inclusive prefix at the last valid row
+#pragma unroll
+  for (int j = AC_T - 1; j >= 0; --j) {
+    if (j < v) {
+      const bool pos = (f >> j) & 1u;
+      if ((en >> j) & 1u) cur = cp;
+      if (!pos && s[j] != bfirst && s[j] != blast) acc += cur;
+      cp -= pos;
+    }
+  }
+  const long long edges = ac_block_sum((long long)lead_p | ((long long)lead_n << 16) | ((long long)trail_p << 32)
+                                       | ((long long)trail_n << 48), red, lane, wv);
+  const long long inner = ac_block_sum(acc | ((long long)int_n << 40), red, lane, wv);
+  if (tid == 0) {
+    long long* o = a.summ + (long long)blockIdx.x * AC_SUMMARY;
+    o[0] = __double_as_longlong(bfirst);
+    o[1] = __double_as_longlong(blast);
+    o[2] = edges & 0xffff;
+    o[3] = (edges >> 16) & 0xffff;
+    o[4] = (edges >> 32) & 0xffff;
+    o[5] = (edges >> 48) & 0xffff;
+    o[6] = tot_p;
+    o[7] = nb - tot_p;
+    o[8] = inner & ((1LL << 40) - 1);
+    o[9] = inner >> 40;
+  }
+}
+
+// Inclusive and exclusive scan of one int64 per thread over the AC_CTHREADS threads of the combine workgroup (MAX:
+// running maximum with identity -1, else running sum); *total = the scan's last value.
+template <bool MAX>
+__device__ __forceinline__ long long ac_scan(long long v, long long* lds, int lane, int wv, long long* excl,
+                                             long long* total) {
+  const long long id = MAX ? -1LL : 0LL;
+  long long x = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const long long t = __shfl_up(x, d, 64);
+    if (lane >= d) x = MAX ? (t > x ? t : x) : x + t;
+  }
+  long long e = __shfl_up(x, 1, 64);
+  if (lane == 0) e = id;
+  __syncthreads();
+  if (lane == 63) lds[wv] = x;
+  __syncthreads();
+  long long pre = id, tot = id;
+  for (int w = 0; w < AC_CTHREADS / 64; ++w) {
+    const long long t = lds[w];
+    if (w < wv) pre = MAX ? (t > pre ? t : pre) : pre + t;
+    tot = MAX ? (t > tot ? t : tot) : tot + t;
+  }
+  *excl = MAX ? (pre > e ? pre : e) : pre + e;
+  *total = tot;
+  return MAX ? (pre > x ? pre : x) : pre + x;
+}
+
+// The runs' edge tie groups form a sequence L_0 T_0 L_1 T_1 ... (leading / trailing group of every run; a run that is
+// one tie group has only L). Neighbours with equal scores chain into one tie group; a chain with N negatives, P_head
+// positives before it and P_tail positives through its end adds N (P_head + P_tail). Both P_head and the negatives
+// before the chain are values AT the chain's head, and both are non-decreasing along the sequence, so "the value at
+// the latest head" is a running maximum: two prefix sums and two max-scans over the runs, no serial walk. One thread
+// per run, AC_CTHREADS runs per round, the scans' totals carried from round to round.
+__global__ __launch_bounds__(AC_CTHREADS) void auc_count_combine_kernel(AucCountArgs a) {
+  __shared__ long long lds[AC_CTHREADS / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  long long acc = 0;
+  long long carryP = 0, carryN = 0, carryHp = -1, carryHn = -1;
+  for (long long b0 = 0; b0 < a.n_blocks; b0 += AC_CTHREADS) {
+    const long long b = b0 + tid;
+    const bool live = b < a.n_blocks;
+    double first = 0.0, last = 0.0;
+    long long q2 = 0, q3 = 0, q4 = 0, q5 = 0, tp = 0, tn = 0, q8 = 0, q9 = 0;
+    bool hL = false, tT = false;
+    if (live) {
+      const long long* q = a.summ + b * AC_SUMMARY;
+      first = __longlong_as_double(q[0]);
+      last = __longlong_as_double(q[1]);
+      q2 = q[2]; q3 = q[3]; q4 = q[4]; q5 = q[5]; tp = q[6]; tn = q[7]; q8 = q[8]; q9 = q[9];
+      hL = b == 0 || first != __longlong_as_double(q[1 - AC_SUMMARY]);             // last score of the run before
+      tT = b == a.n_blocks - 1 || last != __longlong_as_double(q[AC_SUMMARY]);       // first score of the next run
+    }
+    const bool single = first == last;                        // (idle threads: an empty single run, no head, no tail)
+    const long long pL = single ? tp : q2, nL = single ? tn : q3, pT = single ? 0 : q4, nT = single ? 0 : q5;
+    long long exP, totP, exN, totN;
+    ac_scan<false>(tp, lds, lane, wv, &exP, &totP);
+    ac_scan<false>(nL + nT, lds, lane, wv, &exN, &totN);
+    const long long Pb = carryP + exP, Nb = carryN + exN;     // positives / edge negatives before this run
+    // the run's latest head: T when the run has two groups, else L when it starts a chain
+    const long long mHp = !live ? -1 : !single ? Pb + tp - pT : hL ? Pb : -1;
+    const long long mHn = !live ? -1 : !single ? Nb + nL : hL ? Nb : -1;
+    long long exHp, totHp, exHn, totHn;
+    ac_scan<true>(mHp, lds, lane, wv, &exHp, &totHp);
+    ac_scan<true>(mHn, lds, lane, wv, &exHn, &totHn);
+    if (live) {
+      const long long inHp = exHp > carryHp ? exHp : carryHp, inHn = exHn > carryHn ? exHn : carryHn;
+      const long long HpL = hL ? Pb : inHp, HnL = hL ? Nb : inHn;
+      long long HpT = HpL, HnT = HnL;
+      if (!single) {
+        acc += q8 + 2 * Pb * q9;                              // interior tie groups
+        acc += (Nb + nL - HnL) * (HpL + Pb + pL);             // L closes a chain
+        HpT = Pb + tp - pT;
+        HnT = Nb + nL;
+      }
+      if (tT) acc += (Nb + nL + nT - HnT) * (HpT + Pb + tp);
+    }
+    carryP += totP;
+    carryN += totN;
+    carryHp = totHp > carryHp ? totHp : carryHp;
+    carryHn = totHn > carryHn ? totHn : carryHn;
+  }
+  long long ex, tot;
+  ac_scan<false>(acc, lds, lane, wv, &ex, &tot);
+  if (tid == 0) {
+    a.out[0] = tot;
+    a.out[1] = carryP;
+    a.out[2] = a.n - carryP;
+  }
+}
+
 extern "C" {
 
 const char* pml_build_id() { return pml_build_stamp + 13; }
+
+int pml_auc_count_block_rows() { return AC_ROWS; }
+
+// a->out[3] = (2 raw, positives, negatives) of a->n > 0 sorted rows; a->summ: a->n_blocks * AC_SUMMARY int64 of
+// workspace, n_blocks = ceil(n / AC_ROWS). Both input streams must be 16-byte aligned.
+int pml_auc_counts(const AucCountArgs* a, void* stream) {
+  if (a->n <= 0) return -22;
+  const long long blocks = (a->n + AC_ROWS - 1) / AC_ROWS;
+  if (blocks != a->n_blocks || blocks > 0x7fffffffLL || a->n >= (1LL << 31)) return -22;
+  if (((uintptr_t)a->scores & 15) || ((uintptr_t)a->flag & 15)) return -22;
+  hipLaunchKernelGGL(auc_count_kernel, dim3((unsigned)blocks), dim3(AC_THREADS), 0, (hipStream_t)stream, *a);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(auc_count_combine_kernel, dim3(1), dim3(AC_CTHREADS), 0, (hipStream_t)stream, *a);
+  LAUNCH_CHECK();
+  return 0;
+}
 
 // Per-group ranking metric of the groups a->list of one size class (cls 0: C16, 1: C64, 2: CWG, 3: LONG / pre-sorted)
 // into a->out; k = 0: AUC, k > 0: precision@k. npad_max (CWG): a power of two >= the longest listed group, <= 4096.

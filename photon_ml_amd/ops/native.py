@@ -73,6 +73,12 @@ class SegRankArgs(ctypes.Structure):
                 ("n_groups", ctypes.c_longlong), ("k", c_int)]
 
 
+class AucCountArgs(ctypes.Structure):
+    """Arguments of the sorted-stream AUC count kernels (``auc_count_*_kernel``, ops/csrc/game_kernels.hip)."""
+    _fields_ = [("scores", c_void_p), ("flag", c_void_p), ("summ", c_void_p), ("out", c_void_p),
+                ("n", ctypes.c_longlong), ("n_blocks", ctypes.c_longlong)]
+
+
 class TLTDesc(ctypes.Structure):
     _fields_ = [
         ("items", c_void_p), ("nitems", c_int), ("cbits", c_int), ("pack", c_void_p), ("val", c_void_p),
@@ -709,6 +715,10 @@ def game_lib() -> Optional[ctypes.CDLL]:
         lib.pml_tl_compact.restype = c_int
         lib.pml_seg_rank_eval.argtypes = [c_int, c_int, ctypes.POINTER(SegRankArgs), c_int, c_void_p]
         lib.pml_seg_rank_eval.restype = c_int
+        lib.pml_auc_counts.argtypes = [ctypes.POINTER(AucCountArgs), c_void_p]
+        lib.pml_auc_counts.restype = c_int
+        lib.pml_auc_count_block_rows.argtypes = []
+        lib.pml_auc_count_block_rows.restype = c_int
         for f in ("pml_score_rows", "pml_gemm_nt", "pml_spmm_rows", "pml_downsample"):
             getattr(lib, f).restype = c_int
         lib._pml_typed = True
@@ -891,6 +901,67 @@ def seg_rank_eval(lay, scores: torch.Tensor, k: int = 0) -> Optional[torch.Tenso
     if int(nan_flag.item()):
         return None
     return out[:lay.n_groups]
+
+
+AUC_COUNT_BLOCK_ROWS = 4096     # = AC_ROWS in game_kernels.hip: rows per workgroup of auc_count_kernel
+AUC_COUNT_SUMMARY = 10          # = AC_SUMMARY: int64 slots of one workgroup's summary
+
+
+def check_auc_counts_inputs(scores: torch.Tensor, flags: torch.Tensor) -> None:
+    """Host-side validation of the inputs of :func:`auc_counts` (``PML_CHECK_KERNEL_INPUTS=1``)."""
+    if scores.dtype != torch.float64 or flags.dtype != torch.uint8:
+        raise ValueError(f"auc_counts: scores must be fp64 and flags uint8, got {scores.dtype} / {flags.dtype}")
+    if scores.dim() != 1 or flags.dim() != 1 or scores.numel() != flags.numel():
+        raise ValueError("auc_counts: scores and flags must be 1-D with one entry per row")
+    if not (scores.is_contiguous() and flags.is_contiguous()):
+        raise ValueError("auc_counts: scores and flags must be contiguous")
+    if scores.numel() >= 1 << 31:
+        raise ValueError("auc_counts: at most 2^31 - 1 rows")
+    if scores.numel() > 1 and not bool((scores[1:] <= scores[:-1]).all()):
+        raise ValueError("auc_counts: scores must be sorted non-increasing (and hold no NaN)")
+
+
+def auc_counts(scores: torch.Tensor, flags: torch.Tensor) -> torch.Tensor:
+    """Integer counts of the unweighted tie-grouped AUC of ONE stream sorted by score: ``scores`` fp64
+    non-increasing (no NaN), ``flags`` uint8 (non-zero: positive). Returns three int64 on the inputs' device:
+    ``2 raw = sum over tie groups of 2 P_before g_n + g_p g_n`` (``P_before``: positives with a greater score; tie
+    test ``==``), the positives and the negatives; ``AUC = (2 raw / 2) / (P N)``. One streaming pass with many
+    workgroups plus a one-workgroup combine (``auc_count_kernel`` / ``auc_count_combine_kernel``); all sums are
+    integers, so the result has no order dependence. The same counts from torch ops off the GPU."""
+    if os.environ.get("PML_CHECK_KERNEL_INPUTS", "0") == "1":
+        check_auc_counts_inputs(scores, flags)
+    assert scores.dtype == torch.float64 and flags.dtype == torch.uint8 and scores.numel() == flags.numel()
+    n, dev = int(scores.numel()), scores.device
+    if n >= 1 << 31:
+        raise ValueError("auc_counts: at most 2^31 - 1 rows")
+    out = torch.zeros(3, dtype=torch.int64, device=dev)
+    if n == 0:
+        return out
+    if dev.type != "cuda":
+        pos = (flags != 0).to(torch.int64)
+        new = torch.ones(n, dtype=torch.bool)
+        new[1:] = scores[1:] != scores[:-1]
+        gid = torch.cumsum(new.to(torch.int64), 0) - 1
+        ng = int(gid[-1]) + 1
+        gp = torch.zeros(ng, dtype=torch.int64).index_add_(0, gid, pos)
+        gn = torch.zeros(ng, dtype=torch.int64).index_add_(0, gid, 1 - pos)
+        before = torch.cumsum(gp, 0) - gp
+        out[0] = torch.sum(2 * before * gn + gp * gn)
+        out[1], out[2] = gp.sum(), gn.sum()
+        return out
+    assert flags.is_cuda and scores.is_contiguous() and flags.is_contiguous()
+    if scores.data_ptr() % 16:          # the kernel's 16-byte loads (a view that starts inside an allocation)
+        scores = scores.clone()
+    if flags.data_ptr() % 16:
+        flags = flags.clone()
+    nb = -(-n // AUC_COUNT_BLOCK_ROWS)
+    summ = torch.empty(nb * AUC_COUNT_SUMMARY, dtype=torch.int64, device=dev)
+    a = AucCountArgs(scores=scores.data_ptr(), flag=flags.data_ptr(), summ=summ.data_ptr(), out=out.data_ptr(),
+                     n=n, n_blocks=nb)
+    lib = require_game_lib()
+    assert lib.pml_auc_count_block_rows() == AUC_COUNT_BLOCK_ROWS
+    check(lib.pml_auc_counts(ctypes.byref(a), stream_handle(dev)), "auc_counts")
+    return out
 
 
 def sorted_counts(sorted_keys: torch.Tensor, nbins: int) -> torch.Tensor:

@@ -29,7 +29,8 @@ def runtime_warmup(device, force: bool = False) -> float:
         return 0.0
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
-    from .native import batched_gemv, batched_trsv, check_lds_add_order, csr_gather_rows, key_histogram
+    from .native import (auc_counts, batched_gemv, batched_trsv, check_lds_add_order, csr_gather_rows,
+                         key_histogram)
     x = torch.linspace(0.0, 1.0, 4096, dtype=torch.float64, device=dev)
     i = torch.arange(4096, dtype=torch.int64, device=dev)
     # torch kernel families of the optimizers, the score algebra and the solver setup
@@ -55,6 +56,7 @@ def runtime_warmup(device, force: bool = False) -> float:
     key_histogram(i % 13, 13)                                            # libpml_game
     csr_gather_rows(torch.tensor([0, 2], dtype=torch.int64, device=dev), i[:2], x[:2],
                     torch.zeros(1, dtype=torch.int64, device=dev), torch.tensor([0, 4], dtype=torch.int64, device=dev))
+    auc_counts(x.flip(0).contiguous(), (i % 2).to(torch.uint8))
     L = torch.eye(65, dtype=torch.float64, device=dev).unsqueeze(0).contiguous()
     batched_trsv(L, torch.ones(1, 65, dtype=torch.float64, device=dev))  # libpml_re (n > 64)
     batched_gemv(L[:, :8, :8].contiguous(), torch.ones(1, 8, dtype=torch.float64, device=dev))

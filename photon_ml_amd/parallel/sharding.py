@@ -11,6 +11,11 @@ C8). The permutation is kept, so each coordinate update moves only N-length fp64
 owners (C11) and new scores back (C12) — two ``all_to_all_single`` calls over xGMI per RE update instead of two
 shuffles. Entity ownership is computed identically on every rank from all-gathered (entity key, count) pairs
 (C9), so no broadcast is needed.
+
+The validation metrics use the same pieces (``evaluation/evaluators.py``): ``AUC:tag`` / ``PRECISION@k:tag`` route
+every row once to the owner of its GROUP (``entity_keys`` -> ``EntityPartitioner.build_t`` -> ``RowRouter``) and an
+evaluation routes only the scores (C18); plain AUC exchanges score buckets whose segments change every call through
+``RowRouter.from_counts`` / ``exchange`` (C17).
 """
 from __future__ import annotations
 
@@ -234,6 +239,36 @@ class RowRouter:
             self.recv_counts = list(self.send_counts)
         self.n_recv = int(sum(self.recv_counts))
         self.src_rank = np.repeat(np.arange(P), self.recv_counts)
+
+    @classmethod
+    def from_counts(cls, send_counts: Sequence[int], group=None) -> "RowRouter":
+        """A router for rows that are ALREADY grouped by destination (``send_counts[p]`` rows for rank p, in
+        order): no permutation, :meth:`exchange` only. Used by exchanges whose segments change every call (the
+        score buckets of the global AUC), which keep the bounded-round device all-to-all of :meth:`_a2a`."""
+        self = cls.__new__(cls)
+        self.group = group
+        self._perm_on = {}
+        self.perm = None
+        self.send_counts = [int(c) for c in send_counts]
+        self.n_local = int(sum(self.send_counts))
+        if is_dist():
+            dev = comm_device(group)
+            sc = torch.tensor(self.send_counts, dtype=torch.int64, device=dev)
+            rc = torch.empty_like(sc)
+            dist.all_to_all_single(rc, sc, group=group)
+            self.recv_counts = [int(x) for x in rc.tolist()]
+        else:
+            self.recv_counts = list(self.send_counts)
+        self.n_recv = int(sum(self.recv_counts))
+        self.src_rank = None                     # per-row table: not built for a per-call router
+        return self
+
+    def exchange(self, send: torch.Tensor) -> torch.Tensor:
+        """All-to-all of rows already grouped by destination (no permutation): the concatenation over source
+        ranks of the segments sent here, on ``send``'s device."""
+        if not is_dist():
+            return send
+        return self._a2a(send, self.send_counts, self.recv_counts)[0]
 
     def perm_on(self, device) -> torch.Tensor:
         """The routing permutation as an int64 tensor on ``device`` (uploaded once per device)."""
