@@ -197,6 +197,7 @@ class Driver:
         self.validation_data: Optional[LabeledData] = None
         self.index_map = None
         self.summary = None
+        self.glm_data = None          # device copy of the training shard (built with the statistics, see preprocess)
         self.normalization: Optional[NormalizationContext] = None
         self.lambda_models: List[Tuple[float, object]] = []
         self.trackers = {}
@@ -299,7 +300,11 @@ class Driver:
                          {"features": self.validation_data.x}, a.data_validation_type)
         norm = NormalizationType.parse(a.normalization_type)
         if a.summarization_output_dir or norm != NormalizationType.NONE:
-            self.summary = BasicStatisticalSummary.compute(self.train_data.x)
+            # the training shard goes to the device once, here: its statistics come from that copy when it is
+            # tiled, on a GPU and stored in fp64 (host otherwise), and training reuses it (glm_data=)
+            from ..ops.backend import make_glm_data
+            self.glm_data = make_glm_data(self.train_data, a.device, a.precision)
+            self.summary = BasicStatisticalSummary.for_shard(self.train_data.x, self.glm_data)
             if a.summarization_output_dir:
                 os.makedirs(a.summarization_output_dir, exist_ok=True)
                 save_feature_summary(os.path.join(a.summarization_output_dir, "part-00000.avro"), self.summary,
@@ -313,7 +318,8 @@ class Driver:
             data, self.task, a.optimizer, self.reg, [float(x) for x in split_list([a.regularization_weights])],
             self.normalization, a.num_iterations, a.convergence_tolerance,
             constraint_map_from_json(a.coefficient_box_constraints, self.index_map), warm, a.use_warm_start,
-            device=a.device, precision=a.precision)
+            device=a.device, precision=a.precision,
+            glm_data=self.glm_data if data is self.train_data else None)
         return res
 
     def train(self):

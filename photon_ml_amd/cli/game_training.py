@@ -4,9 +4,11 @@ Reference: ``photon-client/.../cli/game/GameDriver.scala:43-260`` (shared params
 off-heap index map directory or a feature-bags directory, date-range input paths) and
 ``cli/game/training/GameTrainingDriver.scala:63-720``:
 
-  clean output dirs -> feature maps -> read train / validation -> validate -> per-shard statistics (written to
-  ``--data-summary-directory/<shard>``) -> normalization contexts -> λ grid (cartesian product over coordinates)
-  -> ``GameEstimator.fit`` -> optional hyper-parameter tuning (needs validation data) -> select models by the first
+  clean output dirs -> feature maps -> read train / validation -> validate -> λ grid (cartesian product over
+  coordinates) -> ``GameEstimator.fit``, which builds the coordinates, takes the per-shard statistics of the
+  fixed-effect shards from their device copies (``GameEstimator.set_normalization``; written to
+  ``--data-summary-directory/<shard>`` as soon as the coordinates exist) and builds the normalization contexts
+  -> optional hyper-parameter tuning (needs validation data) -> select models by the first
   validation evaluator -> save ``best/`` and ``models/<i>/`` (each with a ``model-spec`` text file).
 
 Usage::
@@ -48,7 +50,7 @@ from ..io.data_reader import AvroDataReader, InputColumnNames
 from ..io.index_map import index_map_from_feature_bags, open_index_map
 from ..io.model_io import save_game_model
 from ..io.score_io import save_feature_summary
-from ..normalization.context import NormalizationContext, NormalizationType
+from ..normalization.context import NormalizationType
 from ..parallel.dist import is_dist, rank, world_size
 from ..stat.summary import BasicStatisticalSummary
 from ..utils.logging_utils import PhotonLogger
@@ -259,22 +261,29 @@ class GameTrainingDriver(GameDriverBase):
             for d in [train] + ([validation] if validation is not None else []):
                 sanity_check(a.training_task, d.response, d.offsets, d.weights, d.shards,
                              DataValidationType.parse(a.data_validation))
-        stats = None
-        if a.data_summary_directory or self.normalization != NormalizationType.NONE:
-            with Timed("Calculate statistics for each feature shard"):
-                stats = {sid: BasicStatisticalSummary.compute(train.shards[sid], all_reduce=is_dist())
-                         for sid in self.shard_configs}
+        # Statistics of a shard a fixed-effect coordinate trains on come from the estimator, which takes them from
+        # the device copy it builds (GameEstimator.set_normalization) and hands them over as soon as the coordinates
+        # exist; every other shard is summarised here, on the host. Random-effect coordinates ignore normalization.
+        def write_summary(sid, st):
             if a.data_summary_directory and rank() == 0:
-                for sid, st in stats.items():
-                    d = os.path.join(a.data_summary_directory, sid)
-                    os.makedirs(d, exist_ok=True)
-                    save_feature_summary(os.path.join(d, "part-00000.avro"), st, maps[sid])
-        norm_ctx = {}
-        if self.normalization != NormalizationType.NONE:
-            shard_ctx = {sid: NormalizationContext.build(self.normalization, st, maps[sid].intercept_index)
-                         for sid, st in stats.items()}
-            norm_ctx = {cid: shard_ctx[cc.data_configuration.feature_shard_id]
-                        for cid, cc in self.coord_configs.items() if not cc.is_random_effect}
+                d = os.path.join(a.data_summary_directory, sid)
+                os.makedirs(d, exist_ok=True)
+                save_feature_summary(os.path.join(d, "part-00000.avro"), st, maps[sid])
+
+        fe_shards = {self.coord_configs[cid].data_configuration.feature_shard_id for cid in self.update_sequence
+                     if not self.coord_configs[cid].is_random_effect}
+        if a.data_summary_directory:
+            with Timed("Calculate statistics for the feature shards no fixed effect trains on"):
+                for sid in self.shard_configs:
+                    if sid not in fe_shards:
+                        write_summary(sid, BasicStatisticalSummary.compute(train.shards[sid], all_reduce=is_dist()))
+        written = set()
+
+        def coordinates_built(estimator):
+            for sid, st in estimator.feature_statistics.items():
+                if sid not in written:
+                    written.add(sid)
+                    write_summary(sid, st)
         configs = expand_game_configurations(self.coord_configs)
         self.log(f"{len(configs)} optimization configuration(s)")
         est = (GameEstimator(device=a.device, precision=a.precision)
@@ -286,7 +295,9 @@ class GameTrainingDriver(GameDriverBase):
                .set_compute_variance(a.compute_variance)
                .set_warm_start(a.use_warm_start)
                .set_tree_aggregate_depth(a.tree_aggregate_depth)
-               .set_coordinate_normalization_contexts(norm_ctx))
+               .set_normalization(self.normalization, {sid: m.intercept_index for sid, m in maps.items()},
+                                  collect_statistics=bool(a.data_summary_directory)))
+        est.coordinates_built_callback = coordinates_built
         if a.model_input_directory:
             from ..io.model_io import load_game_model
             est.set_initial_model(load_game_model(a.model_input_directory, maps))

@@ -60,6 +60,11 @@ class GameEstimator:
         self.coordinate_update_sequence: Optional[List[str]] = None
         self.coordinate_descent_iterations = 1
         self.coordinate_normalization_contexts: Dict[str, NormalizationContext] = {}
+        self.normalization_type = NormalizationType.NONE          # see set_normalization
+        self.intercept_indices_by_shard: Dict[str, Optional[int]] = {}
+        self.collect_statistics = False
+        self.feature_statistics: Dict[str, BasicStatisticalSummary] = {}   # by feature shard id, filled by fit
+        self.coordinates_built_callback = None
         self.compute_variance = False
         self.tree_aggregate_depth = DEFAULT_TREE_AGGREGATE_DEPTH
         self.validation_evaluators: Optional[List[str]] = None
@@ -94,6 +99,31 @@ class GameEstimator:
     def set_coordinate_normalization_contexts(self, ctxs):
         self.coordinate_normalization_contexts = dict(ctxs)
         return self
+
+    def set_normalization(self, normalization_type, intercept_indices_by_shard=None,
+                          collect_statistics: bool = False):
+        """Ask for normalization by TYPE: every fixed-effect coordinate without an explicit context
+        (:meth:`set_coordinate_normalization_contexts` wins per coordinate) gets a ``NormalizationContext`` built
+        from the statistics of the shard the estimator has just put on the device — taken from the device when
+        that shard is tiled, on a GPU and stored in fp64 (``BasicStatisticalSummary.for_shard``), computed on the
+        host otherwise, all-reduced under a process group. ``intercept_indices_by_shard``: feature shard id ->
+        intercept index (or None). ``collect_statistics``: compute and keep the statistics even when the type is
+        NONE (a data summary without normalization). They stay readable in ``feature_statistics`` by shard id, and
+        ``coordinates_built_callback(estimator)`` runs as soon as every coordinate is built, before the first
+        update. Random-effect coordinates ignore normalization."""
+        self.normalization_type = NormalizationType.parse(normalization_type)
+        self.intercept_indices_by_shard = dict(intercept_indices_by_shard or {})
+        self.collect_statistics = bool(collect_statistics)
+        return self
+
+    def _coordinate_statistics(self, data: GameData, shard_id: str, glm_data) -> BasicStatisticalSummary:
+        if shard_id not in self.feature_statistics:
+            from ..utils.timing import Timed
+            where = "device" if BasicStatisticalSummary.on_device(glm_data) else "host"
+            with Timed(f"Calculate statistics for feature shard {shard_id} ({where})"):
+                self.feature_statistics[shard_id] = BasicStatisticalSummary.for_shard(
+                    data.shards[shard_id], glm_data, all_reduce=is_dist())
+        return self.feature_statistics[shard_id]
 
     def set_compute_variance(self, b: bool):
         self.compute_variance = bool(b)
@@ -175,9 +205,16 @@ class GameEstimator:
                 cls = ShardedRandomEffectCoordinate if is_dist() else RandomEffectCoordinate
                 coords[cid] = cls(cid, data, dc, oc, self.training_task, self.compute_variance, self.device)
             else:
-                coords[cid] = FixedEffectCoordinate(cid, data, dc, oc, self.training_task,
-                                                    self.coordinate_normalization_contexts.get(cid),
-                                                    self.compute_variance, self.device, self.precision)
+                explicit = self.coordinate_normalization_contexts.get(cid)
+                co = coords[cid] = FixedEffectCoordinate(cid, data, dc, oc, self.training_task, explicit,
+                                                         self.compute_variance, self.device, self.precision)
+                by_type = explicit is None and self.normalization_type != NormalizationType.NONE
+                if by_type or self.collect_statistics:
+                    st = self._coordinate_statistics(data, co.shard_id, co.glm_data)
+                    if by_type:
+                        co.normalization = NormalizationContext.build(
+                            self.normalization_type, st, self.intercept_indices_by_shard.get(co.shard_id))
+                        co.set_config(oc)
         return coords
 
     def _place(self, data: GameData, seq) -> GameData:
@@ -216,7 +253,10 @@ class GameEstimator:
             if missing:
                 raise ValueError(f"optimization configuration missing coordinates {missing}")
         data = self._place(data, seq)
+        self.feature_statistics = {}
         self.coordinates = self._build_coordinates(data, configurations[0], seq)
+        if self.coordinates_built_callback is not None:
+            self.coordinates_built_callback(self)
         train_eval = build_evaluator(training_loss_evaluator_type(self.training_task), data.response, data.offsets,
                                      data.weights)
         val_evals = self._validation_evaluators(validation) if validation is not None else []

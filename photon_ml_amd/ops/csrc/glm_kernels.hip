@@ -1546,6 +1546,195 @@ static int tl_t_multi_impl(const TLTMultiDesc* c, const void* x, double* G, doub
 }
 
 // ============================================================================================================
+// COLUMN STATISTICS over the transpose copy (K9: per-feature sum, sum of squares, sum of |v|, stored-entry count,
+// max and min; stat/summary.py). The same reduction per column as tl_t_kernel with other accumulators and no
+// gather: an entry contributes f(value) to the LDS slot ``pack & (2^cbits - 1)`` of its item, whatever its row key,
+// so the narrow rounds need neither their bases nor their key windows.
+//
+// The readers below are separate from tl_stream* / tl_narrow (whose code the production kernels keep) and are not
+// pipelined: the pass runs once per fit. They read the layouts of ops/tiled.py: wide rounds lane-interleaved
+// (il = 1: lane L of round r holds logical entries 256 r + L + 64 k in quad element k) or plain (il = 0: 4-aligned
+// quads over [e_lo, e_hi)), narrow rounds as two arrays (8-B pack quad + value quad) or as fused 16-B bf16 lane
+// records (null narrow-value pointer). Padding never counts: a wide entry is live iff its logical index is below
+// e_hi - e_lo (il) / its position is inside [e_lo, e_hi) (plain); narrow rounds are always full.
+//
+// Sums (tl_colsum_kernel, one statistic per launch: 0 sum v, 1 sum v^2, 2 sum |v|, 3 count): fp64 at EVERY width,
+// with the determinism mechanism of the transpose — wave-private LDS rows, each wave walking a fixed share of the
+// rounds in order, rows added in wave order, split tiles through partial rows and tl_t_combine1/2_kernel.
+// LDS budget (64 KB per work-group): NW waves x 2^cbits slots x 8 B for ONE statistic, so
+//   cbits <= 10: 4 waves x 1024 x 8 B = 32 KB;  11: 4 x 2048 x 8 B = 64 KB;  12: 2 waves x 4096 x 8 B = 64 KB
+// (six accumulators per column and wave would need 192 KB at 10 bits). Four launches over a stream that one
+// L-BFGS step reads twice; values are squared / counted exactly in fp64 whatever the stored precision.
+// Max / min (tl_colminmax_kernel, one launch for both) do not depend on the order: work-group-shared LDS slots
+// (2 x 2^cbits x 8 B: 32 KB up to 11 bits, 64 KB at 12) updated with LDS fp64 max / min, then one vector fp64
+// atomic max / min per touched column into the shard-length results (initialised to -inf / +inf by the caller).
+// Instantiations: sums 3 + 3 + 2, max / min 3 + 2 = 13 kernels (an fp64 shard has at most 11 bits).
+// ============================================================================================================
+template <typename VT> __device__ __forceinline__ void cs_vals(const typename TLVals<VT>::Raw& raw, double* v) {
+  typename TLValT<VT>::T t[TL_VEC];
+  TLVals<VT>::get(raw, t);
+#pragma unroll
+  for (int k = 0; k < TL_VEC; ++k) v[k] = static_cast<double>(t[k]);
+}
+
+// f(slot, value) for every stored entry of one item that wave w of NW owns: its share of the narrow rounds, then
+// its share of the wide rounds, each in stream order (a fixed order per wave).
+template <typename VT, int NW, typename F>
+__device__ __forceinline__ void cs_for_each(const int* __restrict__ q, int cbits, const uint32_t* __restrict__ pack,
+                                            const VT* __restrict__ val, const TLNarrow& nar, int il, F f) {
+  typedef typename TLVals<VT>::Raw Raw;
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const uint32_t smask = (1u << cbits) - 1u;
+  const int e_lo = q[1], e_hi = q[2], n_lo = q[4], n_hi = q[5];
+  double v[TL_VEC];
+  {
+    const int nr = n_hi - n_lo;
+    const int r0 = n_lo + (int)(((long long)nr * w) / NW), r1 = n_lo + (int)(((long long)nr * (w + 1)) / NW);
+    bool fused = false;
+    if constexpr (sizeof(VT) == 2) fused = nar.val == nullptr;
+    for (int r = r0; r < r1; ++r) {
+      const size_t e = (size_t)r * TL_ROUND + lane * TL_VEC;
+      v2u pk;
+      if (fused) {
+        if constexpr (sizeof(VT) == 2) {
+          const v4u rec = ldg_nt((const v4u*)(nar.pack + 2 * e));
+          pk.x = rec.x; pk.y = rec.y;
+          v2u u; u.x = rec.z; u.y = rec.w;
+          cs_vals<VT>(u, v);
+        }
+      } else {
+        pk = ldg_nt((const v2u*)(nar.pack + e));
+        const Raw raw = TLVals<VT>::load((const VT*)nar.val + e);
+        cs_vals<VT>(raw, v);
+      }
+      f(pk.x & 0xffffu & smask, v[0]);
+      f((pk.x >> 16) & smask, v[1]);
+      f(pk.y & 0xffffu & smask, v[2]);
+      f((pk.y >> 16) & smask, v[3]);
+    }
+  }
+  if (il) {
+    const int n = e_hi - e_lo;
+    const int nr = (n + TL_ROUND - 1) / TL_ROUND;
+    const int r0 = (int)(((long long)nr * w) / NW), r1 = (int)(((long long)nr * (w + 1)) / NW);
+    for (int r = r0; r < r1; ++r) {
+      const size_t e = (size_t)e_lo + (size_t)r * TL_ROUND + lane * TL_VEC;
+      const v4u pk = ldg_nt((const v4u*)(pack + e));
+      const Raw raw = TLVals<VT>::load(val + e);
+      cs_vals<VT>(raw, v);
+      const int j = r * TL_ROUND + lane;               // logical index of quad element 0
+#pragma unroll
+      for (int k = 0; k < TL_VEC; ++k)
+        if (j + 64 * k < n) f(pk[k] & smask, v[k]);
+    }
+  } else {
+    const int lo = e_lo & ~(TL_VEC - 1);
+    const int nr = (e_hi - lo + TL_ROUND - 1) / TL_ROUND;
+    const int r0 = (int)(((long long)nr * w) / NW), r1 = (int)(((long long)nr * (w + 1)) / NW);
+    for (int r = r0; r < r1; ++r) {
+      const int e = lo + r * TL_ROUND + lane * TL_VEC;
+      if (e >= e_hi) continue;                          // the quad holds no entry of the item
+      const v4u pk = ldg_nt((const v4u*)(pack + e));
+      const Raw raw = TLVals<VT>::load(val + e);
+      cs_vals<VT>(raw, v);
+#pragma unroll
+      for (int k = 0; k < TL_VEC; ++k)
+        if (e + k >= e_lo && e + k < e_hi) f(pk[k] & smask, v[k]);
+    }
+  }
+}
+
+// items: 6 ints {tile, e_lo, e_hi, part, n_lo, n_hi} (TLTChunk). which: 0 sum v, 1 sum v^2, 2 sum |v|, 3 count.
+template <typename VT, int MAXR, int NW>
+__global__ __launch_bounds__(NW * 64) void tl_colsum_kernel(const int* __restrict__ items, int cbits,
+                                                            const uint32_t* __restrict__ pack,
+                                                            const VT* __restrict__ val, TLNarrow nar, int il,
+                                                            int which, double* __restrict__ G, int dim,
+                                                            double* __restrict__ parts) {
+  __shared__ double acc[NW][MAXR];
+  const int* q = items + 6 * blockIdx.x;
+  const int C = 1 << cbits;
+  for (int i = threadIdx.x; i < C; i += NW * 64)
+#pragma unroll
+    for (int w = 0; w < NW; ++w) acc[w][i] = 0.0;
+  __syncthreads();
+  double* mine = acc[threadIdx.x >> 6];
+  cs_for_each<VT, NW>(q, cbits, pack, val, nar, il, [&](uint32_t slot, double v) {
+    const double t = which == 0 ? v : which == 1 ? v * v : which == 2 ? fabs(v) : 1.0;
+    atomicAdd(&mine[slot], t);
+  });
+  __syncthreads();
+  const int c0 = q[0] << cbits, part = q[3];
+  for (int c = threadIdx.x; c < C; c += NW * 64) {
+    double s = acc[0][c];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) s += acc[w][c];
+    if (part < 0) {
+      if (c0 + c < dim) G[c0 + c] += s;
+    } else {
+      parts[(size_t)part * C + c] = s;
+    }
+  }
+}
+
+template <typename VT, int MAXR>
+__global__ __launch_bounds__(NTHREADS) void tl_colminmax_kernel(const int* __restrict__ items, int cbits,
+                                                                const uint32_t* __restrict__ pack,
+                                                                const VT* __restrict__ val, TLNarrow nar, int il,
+                                                                double* __restrict__ mx, double* __restrict__ mn,
+                                                                int dim) {
+  __shared__ double smx[MAXR];
+  __shared__ double smn[MAXR];
+  const int* q = items + 6 * blockIdx.x;
+  const int C = 1 << cbits;
+  for (int i = threadIdx.x; i < C; i += NTHREADS) { smx[i] = -INFINITY; smn[i] = INFINITY; }
+  __syncthreads();
+  cs_for_each<VT, TL_WAVES>(q, cbits, pack, val, nar, il, [&](uint32_t slot, double v) {
+    __hip_atomic_fetch_max(&smx[slot], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_min(&smn[slot], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  });
+  __syncthreads();
+  const int c0 = q[0] << cbits;
+  for (int c = threadIdx.x; c < C; c += NTHREADS) {
+    if (c0 + c >= dim || smx[c] == -INFINITY) continue;       // outside the window / no entry in this item
+    __hip_atomic_fetch_max(&mx[c0 + c], smx[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_min(&mn[c0 + c], smn[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// One chunk: the four sums (each its launch + the split tiles' combine, sharing ``parts``), then max / min; all on
+// ``st``, adding into the caller's window of the shard-length results. -22: a width the value type does not have.
+template <typename VT>
+static int tl_colstats_impl(const TLTDesc* c, double* const* sums, double* mx, double* mn, double* parts,
+                            hipStream_t st) {
+  if (c->cbits < 1 || c->cbits > (sizeof(VT) == 8 ? 11 : TL_MAXBITS)) return -22;
+  if (c->nitems <= 0) return 0;
+  for (int which = 0; which < 4; ++which) {
+    auto launch = [&](auto maxr, auto nw) {
+      constexpr int MAXR = decltype(maxr)::value, NW = decltype(nw)::value;
+      hipLaunchKernelGGL((tl_colsum_kernel<VT, MAXR, NW>), dim3(c->nitems), dim3(NW * 64), 0, st, c->items, c->cbits,
+                         c->pack, (const VT*)c->val, c->nar, c->il, which, sums[which], c->dim, parts);
+    };
+    if (c->cbits <= 10) launch(std::integral_constant<int, 1024>{}, std::integral_constant<int, 4>{});
+    else if (c->cbits == 11) launch(std::integral_constant<int, 2048>{}, std::integral_constant<int, 4>{});
+    else if constexpr (sizeof(VT) != 8) launch(std::integral_constant<int, 4096>{}, std::integral_constant<int, 2>{});
+    LAUNCH_CHECK();
+    const int rc = tl_t_combine(c, sums[which], parts, st);
+    if (rc) return rc;
+  }
+  auto launch_mm = [&](auto maxr) {
+    constexpr int MAXR = decltype(maxr)::value;
+    hipLaunchKernelGGL((tl_colminmax_kernel<VT, MAXR>), dim3(c->nitems), dim3(NTHREADS), 0, st, c->items, c->cbits,
+                       c->pack, (const VT*)c->val, c->nar, c->il, mx, mn, c->dim);
+  };
+  if (c->cbits <= 11) launch_mm(std::integral_constant<int, 2048>{});
+  else if constexpr (sizeof(VT) != 8) launch_mm(std::integral_constant<int, 4096>{});
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// ============================================================================================================
 // Segmented dot products for the block-diagonal random-effect solver: out[s] = sum_{i in [ptr[s], ptr[s+1])} f(a_i,
 // b_i) with f = a*b (mode 0), a (mode 1), |a| (mode 2). One wave per segment, lane-strided fp64 partial sums
 // combined by a fixed shuffle tree: deterministic, no atomics (replaces scatter-add with heavy contention).
@@ -3769,6 +3958,17 @@ int pml_tl_fwd_multi(int prec, const TLFwdMultiDesc* c, const void* x, int mode,
 int pml_tl_t(int prec, const TLTDesc* c, const void* x, int square, double* G, double* parts, void* stream) {
   return with_prec_sq(prec, square, [&](auto vt, auto xt, auto sq) {
     return tl_t_impl<decltype(vt), decltype(xt), decltype(sq)::value>(c, x, G, parts, (hipStream_t)stream);
+  });
+}
+
+// Column statistics of one chunk's transpose copy (see COLUMN STATISTICS): sums = {sum v, sum v^2, sum |v|,
+// count}, each with >= c->dim doubles at the chunk's column window, like mx / mn (which the caller initialised to
+// -inf / +inf); parts: the transpose's partial-row scratch.
+int pml_tl_colstats(int prec, const TLTDesc* c, double* s1, double* s2, double* sabs, double* cnt, double* mx,
+                    double* mn, double* parts, void* stream) {
+  double* const sums[4] = {s1, s2, sabs, cnt};
+  return with_prec(prec, [&](auto vt, auto) {
+    return tl_colstats_impl<decltype(vt)>(c, sums, mx, mn, parts, (hipStream_t)stream);
   });
 }
 

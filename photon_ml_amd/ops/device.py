@@ -1387,6 +1387,29 @@ class DeviceGLMData(GLMComputable):
         self.t_all(rr, out, square=int(square), build_multi=build_multi)
         return self._unperm(out)
 
+    def column_stats(self):
+        """Per-feature sufficient statistics of the values the shard STORES (the rounded input for bf16 / fp32
+        shards): ``(sum v, sum v^2, sum |v|, stored entries, max, min)``, six fp64 device vectors of length ``dim``
+        in the ORIGINAL feature order (the hottest-first relabel undone, column windows applied). Stored entries
+        count explicit zeros; max / min run over stored entries only, so a column without any holds -inf / +inf
+        (:meth:`BasicStatisticalSummary.from_device` applies the implicit-zero and empty-column rules).
+
+        One deterministic pass family over the transpose copies (``tl_colsum_kernel`` / ``tl_colminmax_kernel``,
+        one launch set per chunk in chunk order on the current stream): two calls return the same bits. Needs the
+        tiled layout on a GPU; there is no fall-back."""
+        if self.layout != "tiled" or any(getattr(ch, "kind", None) != "tl" for ch in self.csc):
+            raise ValueError("column_stats needs the tiled layout")
+        if self.device.type != "cuda":
+            raise RuntimeError("column_stats runs the HIP column-statistics kernels: the shard must be on a GPU")
+        from .native import tl_colstats
+        z = lambda: torch.zeros(self.dim, dtype=torch.float64, device=self.device)
+        outs = [z(), z(), z(), z(),
+                torch.full((self.dim,), float("-inf"), dtype=torch.float64, device=self.device),
+                torch.full((self.dim,), float("inf"), dtype=torch.float64, device=self.device)]
+        for c, ch in enumerate(self.csc):
+            tl_colstats(self.prec, ch, self.col_lo[c], outs, self.parts)
+        return tuple(self._unperm(t) for t in outs)
+
     def margins(self, w, margin_shift: float = 0.0, with_offsets: bool = False):
         if (getattr(self, "_masked", None) is None and getattr(self, "z_cache", None) is not None
                 and isinstance(w, torch.Tensor) and self._z_valid_for(w, margin_shift)):

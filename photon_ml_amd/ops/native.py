@@ -136,6 +136,7 @@ def glm_lib() -> Optional[ctypes.CDLL]:
         lib.pml_tl_fwd.argtypes = [c_int, ctypes.POINTER(TLFwdDesc), c_void_p, c_int, c_int, c_double, c_void_p,
                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
         lib.pml_tl_t.argtypes = [c_int, ctypes.POINTER(TLTDesc), c_void_p, c_int, c_void_p, c_void_p, c_void_p]
+        lib.pml_tl_colstats.argtypes = [c_int, ctypes.POINTER(TLTDesc)] + [c_void_p] * 8
         lib.pml_tl_config.argtypes = [c_int, c_int, c_int, c_int]
         lib.pml_tl_t_multi.argtypes = [c_int, ctypes.POINTER(TLTMultiDesc), c_void_p, c_int, c_void_p, c_void_p,
                                        c_void_p]
@@ -189,6 +190,7 @@ def glm_lib() -> Optional[ctypes.CDLL]:
         lib.pml_rs_tron.argtypes = [c_int, c_int] + [c_void_p] * 8 + [c_int, c_double, c_double, c_int, c_int, c_int,
                                                                       c_void_p, c_void_p, c_void_p]
         for f in ("pml_seg_fwd", "pml_seg_t", "pml_reduce_stats", "pml_build_blocks", "pml_tl_fwd", "pml_tl_t",
+                  "pml_tl_colstats",
                   "pml_tl_maxbits", "pml_segdot", "pml_segdot_long", "pml_tl_fwd_multi", "pml_tl_t_multi", "pml_seg_cg_step",
                   "pml_seg_expand", "pml_bgemv", "pml_btrsv", "pml_bhv", "pml_rs_tron", "pml_ls_eval", "pml_gram_grid", "pml_gram",
                   "pml_lincomb", "pml_lbfgs_pair", "pml_ls_dots", "pml_two_loop_chain", "pml_two_loop_gram",
@@ -409,6 +411,82 @@ def perm_cast(w: torch.Tensor, perm: Optional[torch.Tensor], dtype: torch.dtype)
                                           2 if dtype == torch.float64 else 1, out.data_ptr(), stream_handle(w.device)),
           "perm_cast")
     return out
+
+
+def check_tl_colstats_inputs(ch, col_lo: int, outs, parts: torch.Tensor) -> None:
+    """Host-side validation of everything ``tl_colsum_kernel`` / ``tl_colminmax_kernel`` and the combine index
+    through for one transpose chunk (``PML_CHECK_KERNEL_INPUTS=1``) — on its own, so that a chunk that never went
+    through ``DeviceGLMData.validate`` is covered too: the width, the item windows as THESE readers walk them (whole
+    256-entry rounds in the interleaved layout, whole quads in the plain one), the narrow rounds against the narrow
+    streams, the partial-row slots and combine tables against ``parts``, and the six result buffers against the
+    chunk's column window (the last tile may be partial: the kernels write columns < ``ch.dim`` only)."""
+    C = 1 << ch.cbits
+    f64 = ch.val.dtype == torch.float64
+    if not 1 <= ch.cbits <= (11 if f64 else 12):
+        raise ValueError(f"column statistics: tile width {ch.cbits} bits not supported for {ch.val.dtype}")
+    if len(outs) != 6 or col_lo < 0:
+        raise ValueError("column statistics: six result buffers and a non-negative column window base")
+    for t in outs:
+        if not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.device == ch.pack.device
+                and t.numel() >= col_lo + ch.dim):
+            raise ValueError(f"column statistics: result buffers must be fp64 device vectors of at least "
+                             f"{col_lo + ch.dim} elements (window base {col_lo} + {ch.dim} columns)")
+    if not (parts.is_cuda and parts.dtype == torch.float64 and parts.is_contiguous()
+            and parts.numel() >= max(ch.parts_needed, 1)):
+        raise ValueError("column statistics: partial-row scratch too small")
+    if ch.pack.dtype != torch.int32 or ch.pack.numel() != ch.val.numel() or not ch.pack.is_contiguous() \
+            or not ch.val.is_contiguous():
+        raise ValueError("column statistics: wide streams must be contiguous int32 packs and as many values")
+    if ch.nitems == 0:
+        return
+    it = ch.items.cpu().to(torch.int64)
+    if it.shape != (ch.nitems, 6) or ch.items.dtype != torch.int32 or not ch.items.is_contiguous():
+        raise ValueError("column statistics: item table must be [nitems, 6] int32")
+    tile, e_lo, e_hi, part, n_lo, n_hi = (it[:, k] for k in range(6))
+    if int(tile.min()) < 0 or int(tile.max()) * C >= max(ch.dim, 1):
+        raise ValueError("column statistics: item tile outside the chunk's columns")
+    if bool((e_hi < e_lo).any()) or int(e_lo.min()) < 0:
+        raise ValueError("column statistics: item window reversed or negative")
+    if ch.il:
+        end = e_lo + (e_hi - e_lo + 255) // 256 * 256
+        if bool((e_lo % 256 != 0).any()) or int(end.max()) > ch.pack.numel():
+            raise ValueError("column statistics: interleaved item windows must be whole rounds inside the stream")
+    elif int(((e_hi + 3) // 4 * 4).max()) > ch.pack.numel():
+        raise ValueError("column statistics: item window quads outside the stream")
+    if bool((n_hi < n_lo).any()) or int(n_lo.min()) < 0:
+        raise ValueError("column statistics: narrow round range reversed or negative")
+    top = int(n_hi.max())
+    if top > 0:
+        if ch.fused:
+            ok = ch.val.element_size() == 2 and ch.nrec.is_contiguous() and ch.nrec.numel() >= 512 * top
+        else:
+            ok = (ch.npack.is_contiguous() and ch.nval.is_contiguous() and ch.npack.numel() >= 256 * top
+                  and ch.nval.numel() >= 256 * top and ch.nval.dtype == ch.val.dtype)
+        if not ok:
+            raise ValueError("column statistics: narrow streams shorter than the items' rounds")
+    if int(part.min()) < -1 or int(part.max()) >= ch.nparts:        # -1: the tile's only item
+        raise ValueError("column statistics: partial-row slot out of range")
+    if ch.nmt:
+        cu = ch.cu.cpu().to(torch.int64)[: ch.ncu]
+        mp = ch.mt_ptr.cpu().to(torch.int64)
+        mt = ch.mt_tiles.cpu().to(torch.int64)[: ch.nmt]
+        if (cu.shape[0] != ch.ncu or mp.numel() < ch.nmt + 1 or mt.numel() != ch.nmt
+                or int(cu[:, 1].min()) < 0 or bool((cu[:, 2] < cu[:, 1]).any()) or int(cu[:, 2].max()) > ch.nparts
+                or int(mp.min()) < 0 or int(mp[: ch.nmt + 1].max()) > ch.ncu
+                or int(mt.min()) < 0 or int(mt.max()) * C >= ch.dim):
+            raise ValueError("column statistics: combine tables outside the partial rows / the chunk's columns")
+
+
+def tl_colstats(prec: int, ch, col_lo: int, outs, parts: torch.Tensor) -> None:
+    """Add the column statistics of one transpose chunk (``ops.tiled.TLTChunk``) into ``outs`` = (sum v, sum v^2,
+    sum |v|, count, max, min), shard-length fp64 device vectors in DEVICE column order, at the chunk's column window
+    ``col_lo`` (max / min start at -inf / +inf). ``tl_colsum_kernel`` x 4 + combine, ``tl_colminmax_kernel``;
+    deterministic (glm_kernels.hip, COLUMN STATISTICS)."""
+    if os.environ.get("PML_CHECK_KERNEL_INPUTS", "0") == "1":
+        check_tl_colstats_inputs(ch, col_lo, outs, parts)
+    ptrs = [t.data_ptr() + 8 * col_lo for t in outs]
+    check(require_glm_lib().pml_tl_colstats(prec, ctypes.byref(ch.desc), *ptrs, parts.data_ptr(),
+                                            stream_handle(ch.pack.device)), "tl_colstats")
 
 
 def offset_update(base: torch.Tensor, part: torch.Tensor, o: torch.Tensor, z: Optional[torch.Tensor]) -> None:

@@ -77,11 +77,29 @@ class BasicStatisticalSummary:
         return BasicStatisticalSummary.from_sufficient(count, s1, s2, sabs, nnz, mx, mn)
 
     @staticmethod
-    def from_device(data, all_reduce: bool = False) -> "BasicStatisticalSummary":
-        """Same statistics straight from a device-resident shard (``ops.device.DeviceGLMData``, tiled layout):
-        column reductions over the forward streams with device scatter-reductions, no host copy of the
-        non-zeros (K9 on the GPU); with ``all_reduce`` the sufficient statistics are reduced over the process
-        group (C24). Feature order: original (the device relabelling is undone)."""
+    def on_device(glm_data) -> bool:
+        """The precision rule of :meth:`for_shard`: a shard's statistics come from the device when it is in the
+        tiled layout, on a GPU and stored in fp64 — then the stored values ARE the input. bf16 / fp32 shards store
+        the rounded input, and the written summary and the normalization factors must describe the input, so they
+        keep the host path (as do segmented and CPU shards)."""
+        dev = getattr(glm_data, "device", None)
+        return (getattr(glm_data, "layout", None) == "tiled" and dev is not None and dev.type == "cuda"
+                and getattr(glm_data, "precision", None) == "f64")
+
+    @staticmethod
+    def for_shard(x, glm_data, all_reduce: bool = False) -> "BasicStatisticalSummary":
+        """Statistics of the feature shard ``x`` (host CSR) whose device copy is ``glm_data``: :meth:`from_device`
+        under the rule of :meth:`on_device`, else :meth:`compute` on the host."""
+        if BasicStatisticalSummary.on_device(glm_data):
+            return BasicStatisticalSummary.from_device(glm_data, all_reduce=all_reduce)
+        if hasattr(x, "to_scipy"):
+            x = x.to_scipy()
+        return BasicStatisticalSummary.compute(x, all_reduce=all_reduce)
+
+    @staticmethod
+    def _torch_column_stats(data):
+        """The six sufficient statistics of a tiled shard with torch scatter-reductions over the forward streams
+        (the CPU path of :meth:`from_device`; ``index_add_`` is not order-deterministic on a GPU)."""
         dev = data.device
         d = data.dim
         f64 = torch.float64
@@ -92,8 +110,6 @@ class BasicStatisticalSummary:
         mx = torch.full((d,), float("-inf"), dtype=f64, device=dev)
         mn = torch.full((d,), float("inf"), dtype=f64, device=dev)
         for c, ch in enumerate(data.csr):
-            if getattr(ch, "kind", None) != "tl":
-                raise ValueError("from_device needs the tiled layout")
             pk, vl = ch.logical()
             col = (pk.to(torch.int64) >> ch.rbits) + data.col_lo[c]     # logical(): non-negative int64
             v = vl.to(f64)
@@ -110,6 +126,25 @@ class BasicStatisticalSummary:
                 out[data.old_of_new] = t
                 return out
             s1, s2, sabs, nnz, mx, mn = (unperm(t) for t in (s1, s2, sabs, nnz, mx, mn))
+        return s1, s2, sabs, nnz, mx, mn
+
+    @staticmethod
+    def from_device(data, all_reduce: bool = False) -> "BasicStatisticalSummary":
+        """Same statistics straight from a device-resident shard (``ops.device.DeviceGLMData``, tiled layout), no
+        host copy of the non-zeros (K9 on the GPU). On a GPU: ``DeviceGLMData.column_stats`` — the deterministic HIP
+        column reduction over the transpose copies (fp64 sums, bitwise repeatable). On the CPU: torch
+        scatter-reductions over the forward streams. The statistics describe the values the shard stores (bf16 /
+        fp32 shards: the rounded input). With ``all_reduce`` the sufficient statistics are reduced over the process
+        group (C24). Feature order: original (the device relabelling is undone)."""
+        dev = data.device
+        d = data.dim
+        f64 = torch.float64
+        if any(getattr(ch, "kind", None) != "tl" for ch in data.csr):
+            raise ValueError("from_device needs the tiled layout")
+        if dev.type == "cuda":
+            s1, s2, sabs, nnz, mx, mn = data.column_stats()
+        else:
+            s1, s2, sabs, nnz, mx, mn = BasicStatisticalSummary._torch_column_stats(data)
         count = float(data.n_rows)
         if all_reduce:
             from ..parallel.dist import is_dist
