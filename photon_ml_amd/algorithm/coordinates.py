@@ -21,7 +21,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ..constants import EPSILON, TaskType
+from ..constants import EPSILON, TaskType, VarianceComputationType
 from ..utils.timing import Timed, phase
 from ..data.game_data import GameData
 from ..data.matrix import DeviceCSR
@@ -131,14 +131,17 @@ class FixedEffectCoordinate(Coordinate):
                 # the layout, not in the first update (it was ~100 small launches of the cold first sweep)
                 with phase(f"FE {coordinate_id} build: Frobenius norm"):
                     gd.frob_sq()
-        self.compute_variance = compute_variance
+        # a VarianceComputationType or the legacy boolean (True = SIMPLE); FULL: optimization/problem.py
+        self.variance_type = VarianceComputationType.parse(compute_variance)
+        self.compute_variance = self.variance_type != VarianceComputationType.NONE
         self.normalization = normalization
         self.set_config(opt_config)
         self.last_tracker = None
 
     def set_config(self, opt_config: GLMOptimizationConfiguration):
         self.opt_config = opt_config
-        self.problem = GLMOptimizationProblem(opt_config, self.task, self.normalization, self.compute_variance)
+        self.problem = GLMOptimizationProblem(opt_config, self.task, self.normalization, self.variance_type)
+        self.problem.check_full_variance(self.dim, self.coordinate_id)     # before any training
         rate = opt_config.down_sampling_rate
         self.sampler = down_sampler_for_task(self.task, rate) if rate < 1.0 else None
 
@@ -249,7 +252,14 @@ _RS_WARM = object()   # warm-start marker: the last segmented solve kept only ro
 
 
 class RandomEffectCoordinate(Coordinate):
-    """Per-entity GLMs solved in size buckets on the device (K7)."""
+    """Per-entity GLMs solved in size buckets on the device (K7).
+
+    ``compute_variance``: a :class:`VarianceComputationType` or the legacy boolean (True = SIMPLE, ``1 / (H_jj +
+    EPSILON)``). FULL returns ``(H_e^-1)_jj`` per entity (``optimization/variance.py``; on the GPU the HIP routes of
+    ``SegmentedFullVariance``) and needs an L2 weight > 0 (a wide entity's Hessian is singular without it; pure L1
+    counts as 0): checked here and at every ``set_config``. With FULL a segmented coordinate KEEPS its per-entity
+    CSR for its whole life instead of releasing it after the solver setup: 8 B indptr per row plus 16 B (int64
+    column + fp64 value) per non-zero of the active data, on the data's device."""
 
     def __init__(self, coordinate_id: str, data: GameData, data_config: RandomEffectDataConfiguration,
                  opt_config: GLMOptimizationConfiguration, task, compute_variance: bool = False, device=None,
@@ -263,7 +273,8 @@ class RandomEffectCoordinate(Coordinate):
         with phase(f"RE {coordinate_id} build: dataset"):
             self.dataset = RandomEffectDataset(data, data_config, self.device, dtype, entity_subset=entity_subset,
                                                layout=layout)
-        self.compute_variance = compute_variance
+        self.variance_type = VarianceComputationType.parse(compute_variance)
+        self.compute_variance = self.variance_type != VarianceComputationType.NONE
         self.base_offsets = torch.from_numpy(data.offsets).to(self.device)
         self.set_config(opt_config)
         self._W = {}  # projected-space warm-start state per bucket
@@ -310,6 +321,10 @@ class RandomEffectCoordinate(Coordinate):
         if opt_config.optimizer_config.optimizer_type == OptimizerType.TRON and rt in (
                 RegularizationType.L1, RegularizationType.ELASTIC_NET):
             raise ValueError("TRON optimizer incompatible with L1 regularization")
+        if (self.variance_type == VarianceComputationType.FULL and self.loss.twice_differentiable
+                and not opt_config.regularization_context.l2_weight(opt_config.regularization_weight) > 0):
+            raise ValueError(f"coordinate {self.coordinate_id}: FULL variances of a random effect need an L2 "
+                             f"regularization weight > 0")
         self.opt_config = opt_config
         self._reset_warm_state()
 
@@ -374,6 +389,7 @@ class RandomEffectCoordinate(Coordinate):
         ds, cfg = self.dataset, self.opt_config
         keys, vals, vars_ = [], [], []
         iters, reasons = [], []
+        self.last_variance_routes = {}
         t_start = time.time()
         for b, bucket in enumerate(ds.buckets):
             O = ds.bucket_offsets(bucket, offs)
@@ -394,7 +410,8 @@ class RandomEffectCoordinate(Coordinate):
             W = res.W
             var = None
             if self.compute_variance and self.loss.twice_differentiable:
-                var = 1.0 / (bd.hdiag(self.loss, W, l2) + EPSILON)
+                var = (self._full_variance_dense(bd, W, l2) if self._full_var else
+                       1.0 / (bd.hdiag(self.loss, W, l2) + EPSILON))
             k, v, vv = self._to_original(bucket, W, var)
             keys.append(k)
             vals.append(v)
@@ -408,6 +425,55 @@ class RandomEffectCoordinate(Coordinate):
         variances = np.concatenate(vars_) if vars_ else None
         return RandomEffectModel(self.data_config.random_effect_type, self.data_config.feature_shard_id, self.task,
                                  ds.entity_ids, ds.dim, keys, vals, variances)
+
+    @property
+    def _full_var(self) -> bool:
+        return self.variance_type == VarianceComputationType.FULL
+
+    def _log_variance_routes(self, stats: dict):
+        """Once per coordinate: how many entities each FULL-variance route took."""
+        if not getattr(self, "_var_logged", False):
+            self._var_logged = True
+            log.info("RE %s FULL variances: %s", self.coordinate_id, stats)
+        self.last_variance_routes = stats
+
+    def _full_variance_dense(self, bd: BatchedGLMData, W: torch.Tensor, l2: float) -> torch.Tensor:
+        """``(H_b^-1)_jj`` of a dense bucket at ``W`` (HIP factor + column norms on the GPU up to the kernels' cap,
+        the torch definition beyond it and on the CPU)."""
+        from ..optimization.variance import dense_full_variance, dense_full_variance_device
+        c = bd.w * self.loss.dzz(bd.margins(W), bd.y)
+        if bd.X.is_cuda:
+            var, n_torch = dense_full_variance_device(bd.X, c, l2)
+        else:
+            var, n_torch = dense_full_variance(bd.X, c, l2), bd.X.shape[0]
+        stats = dict(getattr(self, "last_variance_routes", None) or {})
+        stats["dense_hip"] = stats.get("dense_hip", 0) + bd.X.shape[0] - n_torch
+        stats["dense_torch"] = stats.get("dense_torch", 0) + n_torch
+        self.last_variance_routes = stats
+        return var.to(W.dtype)
+
+    def _full_variance_segmented(self, W: torch.Tensor, l2: float) -> torch.Tensor:
+        """``(H_e^-1)_jj`` of every entity at ``W`` (packed like the coefficients). The curvature comes from one
+        forward pass at the solution, as the SIMPLE Hessian diagonal's does; entities without active rows get
+        ``1 / l2``. On the GPU: ``SegmentedFullVariance`` (HIP routes for ``min(n_e, d_e) <= 128``, torch beyond);
+        on the CPU the torch definition for every entity."""
+        from ..optimization.variance import SegmentedFullVariance, segmented_full_variance
+        ds = self.dataset
+        seg = ds.seg
+        csr = getattr(ds, "_seg_csr", None)
+        if csr is None:
+            raise RuntimeError("FULL variances need the per-entity CSR of the segmented coordinate")
+        c = seg.w * self.loss.dzz(seg.margins(W), seg.y)
+        if seg.y.device.type == "cuda":
+            plan = getattr(self, "_var_plan", None)
+            if plan is None:
+                plan = self._var_plan = SegmentedFullVariance(seg.row_ptr, seg.col_ptr, csr)
+            var, stats = plan.compute(c, l2)
+        else:
+            var, n = segmented_full_variance(seg.row_ptr, seg.col_ptr, csr, c, l2)
+            stats = {"torch": n}
+        self._log_variance_routes(stats)
+        return var
 
     def _dense_fused(self, b: int, bucket, l1: float):
         """The fused per-entity TRON of a dense bucket (``entity_tron.DenseEntityTronBatch``, built once per
@@ -525,7 +591,8 @@ class RandomEffectCoordinate(Coordinate):
         W = res.W.detach()
         var = None
         if self.compute_variance and self.loss.twice_differentiable:
-            var = 1.0 / (seg.hdiag(self.loss, res.W, l2) + EPSILON)
+            var = (self._full_variance_segmented(res.W, l2) if self._full_var else
+                   1.0 / (seg.hdiag(self.loss, res.W, l2) + EPSILON))
         # the model keeps the projected keys (entity * dim + feature, sorted, aligned with W) without compaction:
         # W is dense in the projected space, and zeros are harmless (dropped at save, <1e-4 as in the reference);
         # compacting 1.25e9 coefficients per update was ~40 GB of traffic at config 5
@@ -565,7 +632,8 @@ class RandomEffectCoordinate(Coordinate):
                 fused = None
             rest = (~done) & (n_e > 0)
             sub = ds.entity_subset(rest) if bool(rest.any()) else None
-            ds.release_csr()
+            if not self._full_var:          # FULL variances read the per-entity CSR at every update
+                ds.release_csr()
             # do the three components' coefficient ranges cover the whole packed vector? Then the model's primal
             # vector needs no zero fill before they write it (each component writes whole entity ranges)
             cov = 0 if rs is None else int((seg.col_ptr[rs.ents + 1] - seg.col_ptr[rs.ents]).sum())
@@ -737,7 +805,8 @@ class RandomEffectCoordinate(Coordinate):
         need_var = self.compute_variance and self.loss.twice_differentiable
         if need_var:
             W = primal()
-            var = 1.0 / (seg.hdiag(self.loss, W, l2) + EPSILON)
+            var = (self._full_variance_segmented(W, l2) if self._full_var else
+                   1.0 / (seg.hdiag(self.loss, W, l2) + EPSILON))
             out = RandomEffectModel(self.data_config.random_effect_type, self.data_config.feature_shard_id,
                                     self.task, ds.entity_ids, ds.dim, ds.projection_keys_t, W, var)
         else:
@@ -795,7 +864,8 @@ class RandomEffectCoordinate(Coordinate):
         if not bool(mask.any()):
             return None
         sub = ds.entity_subset(mask)
-        ds.release_csr()
+        if not self._full_var:
+            ds.release_csr()
         self._sub = (frozen, sub)
         return sub
 

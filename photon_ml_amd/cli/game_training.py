@@ -22,7 +22,12 @@ Usage::
 regularization=L2,reg.weights=0.1|1|10 \\
         --coordinate-configurations name=per-user,feature.shard=user,random.effect.type=userId,optimizer=TRON,\\
 max.iter=20,tolerance=1e-7,regularization=L2,reg.weights=1 \\
-        --coordinate-update-sequence fixed,per-user --coordinate-descent-iterations 2 --evaluators AUC
+        --coordinate-update-sequence fixed,per-user --coordinate-descent-iterations 2 --evaluators AUC \\
+        [--variance-computation-type {NONE,SIMPLE,FULL}]
+
+Coefficient variances: ``--variance-computation-type SIMPLE`` (= the legacy ``--compute-variance true``) writes
+``1 / (H_jj + 1e-12)``, ``FULL`` the inverse-Hessian diagonal ``(H^-1)_jj`` (random effects: per entity, L2 weight > 0
+required; fixed effects: up to 2048 coefficients). Giving both flags with contradicting values is an error.
 
 Multi-GPU: launch with ``torchrun``; each rank reads its slice of the input files and the fixed-effect solves
 all-reduce one packed buffer per evaluation over RCCL (see :mod:`photon_ml_amd.parallel.dist`). Index maps must then
@@ -40,6 +45,7 @@ from typing import Dict, List, Optional
 
 import numpy as np
 
+from ..constants import VarianceComputationType
 from ..data.random_effect import RandomEffectDataConfiguration
 from ..data.validators import DataValidationType, sanity_check
 from ..estimators.game_estimator import GameEstimator, GameResult
@@ -90,8 +96,45 @@ def add_common_arguments(p: argparse.ArgumentParser):
     add_config_arguments(p)
 
 
+class _ComputeVarianceAction(argparse.Action):
+    """``--compute-variance BOOL`` that also records that it was given (for the conflict check with
+    ``--variance-computation-type``)."""
+
+    def __call__(self, parser, namespace, values, option_string=None):
+        setattr(namespace, self.dest, values)
+        namespace._compute_variance_given = True
+
+
+class _TrainingParser(argparse.ArgumentParser):
+    """Resolves the two variance flags after parsing: ``--compute-variance`` alone means SIMPLE, the type alone
+    decides, and a pair that disagrees (``--compute-variance true`` with ``NONE``, ``false`` with ``SIMPLE`` /
+    ``FULL``) is a usage error."""
+
+    def parse_args(self, args=None, namespace=None):
+        ns = super().parse_args(args, namespace)
+        given = ns.__dict__.pop("_compute_variance_given", False)
+        t = getattr(ns, "variance_computation_type", None)
+        if t is not None and given and bool(ns.compute_variance) != (t != VarianceComputationType.NONE.value):
+            self.error(f"--compute-variance {str(bool(ns.compute_variance)).lower()} contradicts "
+                       f"--variance-computation-type {t}")
+        return ns
+
+
+def _variance_type_name(s) -> str:
+    try:
+        return VarianceComputationType.parse(str(s)).value
+    except KeyError:
+        raise ValueError(f"not a variance computation type: {s}")
+
+
+def resolve_variance_type(args) -> VarianceComputationType:
+    """The effective variance computation type of parsed training options."""
+    t = getattr(args, "variance_computation_type", None)
+    return VarianceComputationType.parse(t if t is not None else bool(args.compute_variance))
+
+
 def build_parser() -> argparse.ArgumentParser:
-    p = argparse.ArgumentParser(prog="game-training", description=__doc__.split("\n")[0])
+    p = _TrainingParser(prog="game-training", description=__doc__.split("\n")[0])
     add_common_arguments(p)
     p.add_argument("--training-task", required=True)
     p.add_argument("--validation-data-directories", action="append")
@@ -114,7 +157,13 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--hyper-parameter-tuning-iterations", type=int, default=0)
     p.add_argument("--hyper-parameter-tuning-range", default="1e-4-1e4")
     p.add_argument("--hyper-parameter-tuning-scale", default="LOG", choices=["LOG", "LINEAR"])
-    p.add_argument("--compute-variance", type=parse_bool, default=False)
+    p.add_argument("--compute-variance", type=parse_bool, default=False, action=_ComputeVarianceAction,
+                   help="coefficient variances; alone it means --variance-computation-type SIMPLE")
+    p.add_argument("--variance-computation-type", type=_variance_type_name,
+                   choices=[t.value for t in VarianceComputationType], default=None,
+                   help="NONE, SIMPLE = 1 / (H_jj + 1e-12) (the reciprocal Hessian diagonal) or FULL = (H^-1)_jj "
+                        "(per entity for random effects; fixed effects up to 2048 coefficients; random effects "
+                        "need an L2 weight > 0)")
     p.add_argument("--use-warm-start", type=parse_bool, default=True)
     p.add_argument("--checkpoint-directory", help="save coordinate-descent state after every coordinate update")
     p.add_argument("--model-input-directory",
@@ -292,7 +341,7 @@ class GameTrainingDriver(GameDriverBase):
                                                     for cid, cc in self.coord_configs.items()})
                .set_coordinate_update_sequence(self.update_sequence)
                .set_coordinate_descent_iterations(a.coordinate_descent_iterations)
-               .set_compute_variance(a.compute_variance)
+               .set_variance_computation_type(resolve_variance_type(a))
                .set_warm_start(a.use_warm_start)
                .set_tree_aggregate_depth(a.tree_aggregate_depth)
                .set_normalization(self.normalization, {sid: m.intercept_index for sid, m in maps.items()},

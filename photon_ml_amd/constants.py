@@ -40,6 +40,26 @@ class TaskType(str, enum.Enum):
         return cls[str(s).strip().upper()]
 
 
+class VarianceComputationType(str, enum.Enum):
+    """How coefficient variances are computed: ``NONE`` (no variances), ``SIMPLE`` = ``1 / (H_jj + EPSILON)`` (the
+    reciprocal Hessian diagonal, the reference's only mode) or ``FULL`` = ``(H^-1)_jj`` (the posterior variance under
+    the Laplace approximation; ``optimization/variance.py``)."""
+    NONE = "NONE"
+    SIMPLE = "SIMPLE"
+    FULL = "FULL"
+
+    @classmethod
+    def parse(cls, s: "str | bool | VarianceComputationType | None") -> "VarianceComputationType":
+        """Also accepts the legacy boolean: ``True`` -> SIMPLE, ``False`` / ``None`` -> NONE."""
+        if isinstance(s, VarianceComputationType):
+            return s
+        if s is None:
+            return cls.NONE
+        if isinstance(s, (bool, int)) and not isinstance(s, enum.Enum):
+            return cls.SIMPLE if s else cls.NONE
+        return cls[str(s).strip().upper()]
+
+
 def feature_key(name: str, term: str = "") -> str:
     """Build the canonical ``name\\u0001term`` feature key (Utils.getFeatureKey)."""
     return f"{name}{DELIMITER}{term or ''}"

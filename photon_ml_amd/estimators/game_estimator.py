@@ -26,7 +26,7 @@ import torch
 
 from ..algorithm.coordinate_descent import CoordinateDescent
 from ..algorithm.coordinates import FixedEffectCoordinate, RandomEffectCoordinate, ShardedRandomEffectCoordinate
-from ..constants import RANDOM_SEED, TaskType
+from ..constants import RANDOM_SEED, TaskType, VarianceComputationType
 from ..data.game_data import GameData
 from ..data.matrix import LabeledData
 from ..data.random_effect import FixedEffectDataConfiguration, RandomEffectDataConfiguration
@@ -65,7 +65,7 @@ class GameEstimator:
         self.collect_statistics = False
         self.feature_statistics: Dict[str, BasicStatisticalSummary] = {}   # by feature shard id, filled by fit
         self.coordinates_built_callback = None
-        self.compute_variance = False
+        self.variance_computation_type = VarianceComputationType.NONE   # compute_variance: its boolean view
         self.tree_aggregate_depth = DEFAULT_TREE_AGGREGATE_DEPTH
         self.validation_evaluators: Optional[List[str]] = None
         self.use_warm_start = True
@@ -126,8 +126,23 @@ class GameEstimator:
         return self.feature_statistics[shard_id]
 
     def set_compute_variance(self, b: bool):
+        """Legacy switch: True = SIMPLE variances ``1 / (H_jj + EPSILON)``, False = none."""
         self.compute_variance = bool(b)
         return self
+
+    def set_variance_computation_type(self, t):
+        """``NONE``, ``SIMPLE`` (``1 / (H_jj + EPSILON)``) or ``FULL`` (``(H^-1)_jj``: per entity for random effects,
+        for fixed effects up to 2048 coefficients); see ``constants.VarianceComputationType``."""
+        self.variance_computation_type = VarianceComputationType.parse(t)
+        return self
+
+    @property
+    def compute_variance(self) -> bool:
+        return self.variance_computation_type != VarianceComputationType.NONE
+
+    @compute_variance.setter
+    def compute_variance(self, b):
+        self.variance_computation_type = VarianceComputationType.parse(b)
 
     def set_tree_aggregate_depth(self, d: int):
         if d <= 0:
@@ -203,11 +218,12 @@ class GameEstimator:
             oc = first_cfg[cid]
             if isinstance(dc, RandomEffectDataConfiguration):
                 cls = ShardedRandomEffectCoordinate if is_dist() else RandomEffectCoordinate
-                coords[cid] = cls(cid, data, dc, oc, self.training_task, self.compute_variance, self.device)
+                coords[cid] = cls(cid, data, dc, oc, self.training_task, self.variance_computation_type, self.device)
             else:
                 explicit = self.coordinate_normalization_contexts.get(cid)
                 co = coords[cid] = FixedEffectCoordinate(cid, data, dc, oc, self.training_task, explicit,
-                                                         self.compute_variance, self.device, self.precision)
+                                                         self.variance_computation_type, self.device,
+                                                         self.precision)
                 by_type = explicit is None and self.normalization_type != NormalizationType.NONE
                 if by_type or self.collect_statistics:
                     st = self._coordinate_statistics(data, co.shard_id, co.glm_data)
@@ -350,7 +366,11 @@ def train_generalized_linear_model(data: LabeledData, task, optimizer_type="LBFG
     """ModelTraining.trainGeneralizedLinearModel -> list of (lambda, model, tracker), lambdas DESCENDING.
 
     ``feature_sharded``: under a process group, shard the optimizer state over features instead of replicating
-    it (``parallel/feature_sharding.py``; for models too large to replicate)."""
+    it (``parallel/feature_sharding.py``; for models too large to replicate). ``compute_variance``: a boolean (True =
+    SIMPLE) or a ``VarianceComputationType``; FULL needs at most 2048 coefficients and replicated optimizer state
+    (ValueError before any training otherwise)."""
+    if VarianceComputationType.parse(compute_variance) == VarianceComputationType.FULL and feature_sharded:
+        raise ValueError("FULL variances are not supported with feature-sharded optimizer state")
     device = torch.device(device) if device is not None else default_device()
     gdata = glm_data if glm_data is not None else make_glm_data(data, device, precision)
     view = DistributedGLMData(gdata) if is_dist() and not feature_sharded else gdata

@@ -15,6 +15,8 @@
 //   every group sorted in registers / LDS and evaluated in one pass, one launch per size class.
 // * auc_count_kernel / auc_count_combine_kernel -- integer tie-group counts of the global AUC over one sorted score
 //   stream (plain AUC under a process group: every rank counts the score bucket it received).
+// * var_normal_kernel / var_scale_gram_kernel / chol_colnorm_kernel -- FULL coefficient variances diag(H_e^-1) of the
+//   random-effect entities: per-entity normal matrix, then squared column norms of G^-1 R from its Cholesky factor.
 //
 // Built with: hipcc --offload-arch=gfx950 -O3 -shared -fPIC (photon_ml_amd/ops/build.py). C ABI, ctypes.
 
@@ -468,6 +470,183 @@ __global__ __launch_bounds__(64) void rs_primal_kernel(const long long* __restri
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   }
   for (int j = lane; j < d; j += 64) W[c0 + j] = acc[j];
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// FULL coefficient variances var_j = (H_e^-1)_jj, H_e = X_e^T diag(c) X_e + lam I (optimization/variance.py is the
+// definition; algorithm/coordinates.py dispatches). Both routes end in the squared column norms of G^-1 R for a lower
+// Cholesky factor G of order m = min(n_e, d_e) <= VAR_MMAX:
+//   primal    (d_e <= n_e): A = H_e = G G^T,                      var_j = |G^-1 e_j|^2
+//   row space (n_e <  d_e): A = lam I + B B^T, B = diag(sqrt c) X_e, var_j = (1 - |G^-1 b_j|^2) / lam   (Woodbury)
+// var_normal_kernel / var_scale_gram_kernel form A, batched_chol_kernel factors it, chol_colnorm_kernel does the rest.
+// One wave per entity, launched per size class (n = the class's largest m). No atomics: every LDS address has one
+// owner per step and is updated in a fixed order, so the results are bitwise repeatable.
+// ---------------------------------------------------------------------------------------------------------------
+#define VAR_MMAX 128    // packed factor (66 KB) + one 64-column panel of 128 rows (64 KB) fit the 160 KB of a workgroup
+
+// Primal normal matrix A = lam I + sum_i c_i x_i x_i^T of the entities ents[B] (d_e <= n) as [B, n, n] (symmetric;
+// rows / columns >= d_e: identity). Packed lower triangle in LDS; rows in stored order, the r (r + 1) / 2 pairs
+// (a >= b) of one row's entries on distinct lanes = distinct LDS addresses (rows hold distinct columns).
+__global__ __launch_bounds__(64) void var_normal_kernel(int B, int n, const long long* __restrict__ ents,
+                                                        const long long* __restrict__ row_ptr,
+                                                        const long long* __restrict__ col_ptr,
+                                                        const long long* __restrict__ nip,
+                                                        const long long* __restrict__ pos,
+                                                        const double* __restrict__ val, const double* __restrict__ c,
+                                                        double lam, double* __restrict__ A) {
+  extern __shared__ double Ap[];
+  const int lane = threadIdx.x;
+  const long long b = blockIdx.x;
+  if (b >= B) return;
+  const long long e = ents[b];
+  const long long r0 = row_ptr[e], r1 = row_ptr[e + 1];
+  const long long cb = col_ptr[e];
+  const long long dl = col_ptr[e + 1] - cb;
+  const int de = dl < n ? (int)dl : n;
+  const int np = n * (n + 1) / 2;
+  double* sv = Ap + np;            // the current row's values [n]
+  int* sc = (int*)(sv + n);        // ... and local columns [n] (-1: outside the entity's range, skipped)
+  for (int t = lane; t < np; t += 64) Ap[t] = 0.0;
+  __syncthreads();
+  for (int j = lane; j < de; j += 64) Ap[j * (j + 1) / 2 + j] = lam;
+  for (long long i = r0; i < r1; ++i) {
+    const double ci = c[i];
+    const long long k0 = nip[i];
+    const long long rl = nip[i + 1] - k0;
+    const int r = rl < de ? (int)rl : de;
+    if (ci == 0.0 || r <= 0) continue;          // wave-uniform
+    __syncthreads();
+    for (int t = lane; t < r; t += 64) {
+      const long long col = pos[k0 + t] - cb;
+      const bool ok = col >= 0 && col < de;
+      sc[t] = ok ? (int)col : -1;
+      sv[t] = val[k0 + t];
+    }
+    __syncthreads();
+    const int npair = r * (r + 1) / 2;
+    for (int p = lane; p < npair; p += 64) {
+      int a = (int)((sqrtf(8.0f * (float)p + 1.0f) - 1.0f) * 0.5f);
+      while (a * (a + 1) / 2 > p) --a;
+      while ((a + 1) * (a + 2) / 2 <= p) ++a;
+      const int bb = p - a * (a + 1) / 2;
+      const int ca = sc[a], cq = sc[bb];
+      if (ca < 0 || cq < 0) continue;
+      const int hi = ca > cq ? ca : cq, lo = ca > cq ? cq : ca;
+      const int at = hi * (hi + 1) / 2 + lo;
+      Ap[at] = fma(ci * sv[a], sv[bb], Ap[at]);
+    }
+  }
+  __syncthreads();
+  double* Ab = A + b * (long long)n * n;
+  for (int t = lane; t < n * n; t += 64) {
+    const int i = t / n, k = t - i * n;
+    const int hi = i > k ? i : k, lo = i > k ? k : i;
+    Ab[t] = hi < de ? Ap[hi * (hi + 1) / 2 + lo] : (i == k ? 1.0 : 0.0);
+  }
+}
+
+// Row-space normal matrix in place: K [B, n, n] (seg_gram: X_e X_e^T, zero padded) becomes
+// A = lam I + diag(s) K diag(s), s_i = sqrt(c_i); rows / columns >= n_e: identity.
+__global__ __launch_bounds__(256) void var_scale_gram_kernel(int B, int n, const long long* __restrict__ ents,
+                                                             const long long* __restrict__ row_ptr,
+                                                             const double* __restrict__ c, double lam,
+                                                             double* __restrict__ K) {
+  const long long b = blockIdx.x;
+  if (b >= B) return;
+  const long long e = ents[b];
+  const long long r0 = row_ptr[e];
+  const long long nl = row_ptr[e + 1] - r0;
+  const int ne = nl < n ? (int)nl : n;
+  double* Kb = K + b * (long long)n * n;
+  for (int t = threadIdx.x; t < n * n; t += 256) {
+    const int i = t / n, j = t - i * n;
+    double v = i == j ? 1.0 : 0.0;
+    if (i < ne && j < ne) v = sqrt(c[r0 + i]) * Kb[t] * sqrt(c[r0 + j]) + (i == j ? lam : 0.0);
+    Kb[t] = v;
+  }
+}
+
+// Squared column norms q_j = |G^-1 r_j|^2 for the factors L [B, n, n] (batched_chol_kernel; order nv[b] <= n) of the
+// entities ents[B], written as variances into out at col_ptr[e] + j. The packed factor stays in LDS; the right-hand
+// side is processed in panels of 64 columns, one lane per column: the lane forward-substitutes down its own panel
+// column (LDS, [row][lane]: conflict-free) and accumulates q in fp64 in row order.
+// MODE 0: R = I (primal route), out = q_j for j < min(d_e, nv).
+// MODE 1: R = diag(s) X_e, s = sqrt(c) (row-space route), out = (1 - q_j) / lam for j < d_e; the panel is scattered
+//         from the entity's CSR rows -- the columns inside a row are sorted, so a per-row cursor finds each window.
+template <int MODE>
+__global__ __launch_bounds__(64) void chol_colnorm_kernel(int B, int n, const double* __restrict__ L,
+                                                          const long long* __restrict__ nv,
+                                                          const long long* __restrict__ ents,
+                                                          const long long* __restrict__ row_ptr,
+                                                          const long long* __restrict__ col_ptr,
+                                                          const long long* __restrict__ nip,
+                                                          const long long* __restrict__ pos,
+                                                          const double* __restrict__ val,
+                                                          const double* __restrict__ c, double lam,
+                                                          double* __restrict__ out) {
+  extern __shared__ double Gp[];
+  const int lane = threadIdx.x;
+  const long long b = blockIdx.x;
+  if (b >= B) return;
+  const long long e = ents[b];
+  const long long ml = nv[b];
+  const int m = ml < 0 ? 0 : (ml < n ? (int)ml : n);
+  const long long cb = col_ptr[e];
+  const long long de = col_ptr[e + 1] - cb;
+  const long long ncols = MODE ? de : (de < m ? de : (long long)m);
+  double* panel = Gp + n * (n + 1) / 2;         // [n][64]
+  double* sr = panel + n * 64;                  // MODE 1: s_i [n]
+  int* cur = (int*)(sr + n);                    // MODE 1: next entry of row i (relative to the entity's first) [n]
+  int* end = cur + n;                           // MODE 1: end of row i [n]
+  const double* Lb = L + b * (long long)n * n;
+  for (int t = lane; t < m * n; t += 64) {
+    const int i = t / n, k = t - i * n;
+    if (k <= i) Gp[i * (i + 1) / 2 + k] = Lb[t];
+  }
+  long long e0 = 0;
+  if (MODE) {
+    const long long r0 = row_ptr[e];
+    e0 = nip[r0];
+    for (int i = lane; i < m; i += 64) {
+      sr[i] = sqrt(c[r0 + i]);
+      cur[i] = (int)(nip[r0 + i] - e0);
+      end[i] = (int)(nip[r0 + i + 1] - e0);
+    }
+  }
+  __syncthreads();
+  for (long long j0 = 0; j0 < ncols; j0 += 64) {
+    const long long j = j0 + lane;
+    if (MODE) {
+      for (int i = 0; i < m; ++i) panel[i * 64 + lane] = 0.0;
+      __syncthreads();
+      for (int i = lane; i < m; i += 64) {
+        int k = cur[i];
+        const int ke = end[i];
+        const double s = sr[i];
+        while (k < ke) {
+          const long long col = pos[e0 + k] - cb;
+          if (col >= j0 + 64) break;
+          if (col >= j0) panel[i * 64 + (int)(col - j0)] = s * val[e0 + k];
+          ++k;
+        }
+        cur[i] = k;
+      }
+      __syncthreads();
+    }
+    // identity right-hand sides of this panel are zero above row j0
+    const int i0 = MODE ? 0 : (int)j0;
+    double q = 0.0;
+    for (int i = i0; i < m; ++i) {
+      const int ri = i * (i + 1) / 2;
+      double acc = MODE ? panel[i * 64 + lane] : (i == j ? 1.0 : 0.0);
+      for (int k = i0; k < i; ++k) acc = fma(-Gp[ri + k], panel[k * 64 + lane], acc);
+      const double y = acc / Gp[ri + i];
+      panel[i * 64 + lane] = y;
+      q = fma(y, y, q);
+    }
+    if (j < ncols) out[cb + j] = MODE ? (1.0 - q) / lam : q;
+    __syncthreads();
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1271,6 +1450,60 @@ int pml_rs_primal(int B, int dmax, const long long* ents, const long long* row_p
   LAUNCH_CHECK();
   return 0;
 }
+
+// ---- FULL coefficient variances (var_normal_kernel, var_scale_gram_kernel, chol_colnorm_kernel) ----
+int pml_var_mmax() { return VAR_MMAX; }
+
+// LDS bytes of chol_colnorm_kernel for a class of order n (mode 1 adds the row scales and cursors)
+long long pml_chol_colnorm_lds(int mode, int n) {
+  return ((long long)n * (n + 1) / 2 + 64LL * n + (mode ? 2LL * n : 0)) * (long long)sizeof(double);
+}
+
+// A [B, n, n] = lam I + X_e^T diag(c) X_e for the entities ents[B] (d_e <= n <= VAR_MMAX); c per row of the CSR
+int pml_var_normal(int B, int n, const long long* ents, const long long* row_ptr, const long long* col_ptr,
+                   const long long* nip, const long long* pos, const double* val, const double* c, double lam,
+                   double* A, void* stream) {
+  if (B <= 0) return 0;
+  if (n < 1 || n > VAR_MMAX) return -22;
+  const size_t lds = ((size_t)n * (n + 1) / 2 + n) * sizeof(double) + (size_t)n * sizeof(int) + 8;
+  if (lds > 160 * 1024) return -22;
+  hipLaunchKernelGGL(var_normal_kernel, dim3((unsigned)B), dim3(64), lds, (hipStream_t)stream, B, n, ents, row_ptr,
+                     col_ptr, nip, pos, val, c, lam, A);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// K [B, n, n] (seg_gram) -> lam I + diag(sqrt c) K diag(sqrt c) in place (n <= 192)
+int pml_var_scale_gram(int B, int n, const long long* ents, const long long* row_ptr, const double* c, double lam,
+                       double* K, void* stream) {
+  if (B <= 0) return 0;
+  if (n < 1 || n > 192) return -22;
+  hipLaunchKernelGGL(var_scale_gram_kernel, dim3((unsigned)B), dim3(256), 0, (hipStream_t)stream, B, n, ents, row_ptr,
+                     c, lam, K);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// out[col_ptr[e] + j] = |G^-1 e_j|^2 (mode 0) or (1 - |G^-1 b_j|^2) / lam (mode 1) from the factors L [B, n, n]
+int pml_chol_colnorm(int mode, int B, int n, const double* L, const long long* nv, const long long* ents,
+                     const long long* row_ptr, const long long* col_ptr, const long long* nip, const long long* pos,
+                     const double* val, const double* c, double lam, double* out, void* stream) {
+  if (B <= 0) return 0;
+  if (n < 1 || n > VAR_MMAX || (mode != 0 && mode != 1)) return -22;
+  const long long lds = pml_chol_colnorm_lds(mode, n);
+  if (lds > 160 * 1024) return -22;
+  if (mode) {
+    if (!(lam > 0.0)) return -22;
+    hipLaunchKernelGGL(chol_colnorm_kernel<1>, dim3((unsigned)B), dim3(64), (size_t)lds, (hipStream_t)stream, B, n, L,
+                       nv, ents, row_ptr, col_ptr, nip, pos, val, c, lam, out);
+  } else {
+    hipLaunchKernelGGL(chol_colnorm_kernel<0>, dim3((unsigned)B), dim3(64), (size_t)lds, (hipStream_t)stream, B, n, L,
+                       nv, ents, row_ptr, col_ptr, nip, pos, val, c, lam, out);
+  }
+  LAUNCH_CHECK();
+  return 0;
+}
+
 // counts[nbins] += histogram of keys[n] (int32 if k32 else int64); counts must be zeroed by the caller
 int pml_key_hist(int k32, const void* keys, long long n, long long nbins, unsigned long long* counts, void* stream) {
   if (n <= 0) return 0;

@@ -784,6 +784,16 @@ def game_lib() -> Optional[ctypes.CDLL]:
         lib.pml_seg_gram_set_s.argtypes = [c_int]
         lib.pml_rs_primal.argtypes = [c_int, c_int] + [c_void_p] * 9 + [c_int]
         lib.pml_rs_primal.restype = c_int
+        lib.pml_var_mmax.argtypes = []
+        lib.pml_var_mmax.restype = c_int
+        lib.pml_chol_colnorm_lds.argtypes = [c_int, c_int]
+        lib.pml_chol_colnorm_lds.restype = ctypes.c_longlong
+        lib.pml_var_normal.argtypes = [c_int, c_int] + [c_void_p] * 7 + [c_double, c_void_p, c_void_p]
+        lib.pml_var_normal.restype = c_int
+        lib.pml_var_scale_gram.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p]
+        lib.pml_var_scale_gram.restype = c_int
+        lib.pml_chol_colnorm.argtypes = [c_int, c_int, c_int] + [c_void_p] * 9 + [c_double, c_void_p, c_void_p]
+        lib.pml_chol_colnorm.restype = c_int
         lib.pml_csr_gather_rows.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong,
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         lib.pml_csr_gather_rows.restype = c_int
@@ -1168,6 +1178,167 @@ def rs_primal(ents: torch.Tensor, row_ptr, col_ptr, nip, pos, val, r: torch.Tens
                             t[4].data_ptr(), v.data_ptr(), r.data_ptr(), W.data_ptr(), stream_handle(dev),
                             int(t[4].dtype == torch.int32)),
           "rs_primal")
+
+
+# ---- FULL coefficient variances (var_normal_kernel, var_scale_gram_kernel, chol_colnorm_kernel) ----------------
+VAR_MMAX = 128                 # = VAR_MMAX in game_kernels.hip: largest factor order m = min(n_e, d_e) of the HIP path
+VAR_LDS_MAX = 160 * 1024       # LDS of one workgroup
+VAR_PRIMAL, VAR_ROW_SPACE = 0, 1
+
+
+def chol_colnorm_lds_bytes(mode: int, n: int) -> int:
+    """LDS bytes of ``chol_colnorm_kernel`` for a class of order ``n``: packed factor + one 64-column panel
+    (+ row scales and cursors in row-space mode)."""
+    return (n * (n + 1) // 2 + 64 * n + (2 * n if mode else 0)) * 8
+
+
+def check_var_class(mode: int, n: int, ents: torch.Tensor, row_ptr: torch.Tensor, col_ptr: torch.Tensor,
+                    nv: Optional[torch.Tensor] = None, csr=None, c: Optional[torch.Tensor] = None,
+                    out: Optional[torch.Tensor] = None) -> None:
+    """Host-side check of everything the FULL-variance kernels index by, for one size class (``mode``:
+    ``VAR_PRIMAL`` / ``VAR_ROW_SPACE``; ``n``: the class's padded order). Raises ValueError instead of launching:
+    the class size and its LDS bytes, every ``ents`` value inside the entity range, the members' ``d_e`` (primal) or
+    ``n_e`` (row space) and ``nv`` within ``n``, the row / coefficient / entry vectors long enough. One readback.
+    With ``PML_CHECK_KERNEL_INPUTS=1`` also every column of the members' entries inside the entity's range."""
+    if mode not in (VAR_PRIMAL, VAR_ROW_SPACE):
+        raise ValueError(f"FULL variance: unknown mode {mode}")
+    if not 1 <= int(n) <= VAR_MMAX:
+        raise ValueError(f"FULL variance: class order {n} outside [1, {VAR_MMAX}] (larger entities take the torch path)")
+    lds = chol_colnorm_lds_bytes(mode, int(n))
+    if lds > VAR_LDS_MAX:
+        raise ValueError(f"FULL variance: class order {n} needs {lds} B of LDS > {VAR_LDS_MAX}")
+    nb = int(row_ptr.numel()) - 1
+    if col_ptr.numel() != row_ptr.numel() or nb < 0:
+        raise ValueError("FULL variance: row_ptr / col_ptr do not describe the same entities")
+    for name, t in (("ents", ents), ("row_ptr", row_ptr), ("col_ptr", col_ptr)):
+        if t.dtype != torch.int64 or not t.is_contiguous():
+            raise ValueError(f"FULL variance: {name} must be contiguous int64")
+    if nv is not None and (nv.dtype != torch.int64 or nv.numel() != ents.numel() or not nv.is_contiguous()):
+        raise ValueError("FULL variance: nv must be contiguous int64, one per entity of the class")
+    if ents.numel() == 0:
+        return
+    lo, hi = torch.aminmax(ents)
+    lo, hi = int(lo), int(hi)
+    if lo < 0 or hi >= nb:
+        raise ValueError(f"FULL variance: entity index outside [0, {nb}): [{lo}, {hi}]")
+    d_e = col_ptr[ents + 1] - col_ptr[ents]
+    n_e = row_ptr[ents + 1] - row_ptr[ents]
+    # the members' ranges inside [0, total]: min(first) >= 0 and max(last) <= total, folded into the two minima
+    stats = [torch.minimum(d_e.min(), torch.minimum(col_ptr[ents].min(), (col_ptr[-1] - col_ptr[ents + 1]).min())),
+             d_e.max(),
+             torch.minimum(n_e.min(), torch.minimum(row_ptr[ents].min(), (row_ptr[-1] - row_ptr[ents + 1]).min())),
+             n_e.max(), row_ptr[-1], col_ptr[-1]]
+    if nv is not None:
+        stats += [nv.min(), nv.max(), (nv - (d_e if mode == VAR_PRIMAL else n_e)).max()]
+    if csr is not None:
+        if csr[0].numel() < 2:
+            raise ValueError("FULL variance: empty CSR row pointer")
+        stats += [csr[0][-1], torch.minimum((csr[0][1:] - csr[0][:-1]).min(), csr[0][0])]
+    s = [int(v) for v in torch.stack(stats).tolist()]
+    d_lo, d_hi, n_lo, n_hi, n_rows, d_total = s[:6]
+    if d_lo < 0 or n_lo < 0:
+        raise ValueError("FULL variance: row_ptr / col_ptr not monotone inside [0, total]")
+    if mode == VAR_PRIMAL and d_hi > n:
+        raise ValueError(f"FULL variance: primal class of order {n} holds an entity with {d_hi} coefficients")
+    if mode == VAR_ROW_SPACE and n_hi > n:
+        raise ValueError(f"FULL variance: row-space class of order {n} holds an entity with {n_hi} rows")
+    k = 6
+    if nv is not None:
+        if s[k] < 0 or s[k + 1] > n or s[k + 2] > 0:
+            raise ValueError(f"FULL variance: factor orders outside [0, {n}] or above the entity's size")
+        k += 3
+    if csr is not None:
+        nip, pos, val = csr
+        if nip.dtype != torch.int64 or pos.dtype != torch.int64 or val.dtype != torch.float64:
+            raise ValueError("FULL variance: the CSR must be int64 / int64 / fp64")
+        if nip.numel() < n_rows + 1 or s[k + 1] < 0 or pos.numel() < s[k] or val.numel() < s[k]:
+            raise ValueError("FULL variance: CSR shorter than its row pointers say")
+        if s[k] >= 2 ** 31:
+            raise ValueError("FULL variance: more than 2^31 entries")
+    if c is not None and (c.dtype != torch.float64 or c.numel() < n_rows or not c.is_contiguous()):
+        raise ValueError("FULL variance: the row curvature must be contiguous fp64, one per row")
+    if out is not None and (out.dtype != torch.float64 or out.numel() < d_total or not out.is_contiguous()):
+        raise ValueError("FULL variance: the variance vector must be contiguous fp64, one per coefficient")
+    if csr is not None and os.environ.get("PML_CHECK_KERNEL_INPUTS", "0") == "1":
+        nip, pos, _ = csr
+        dev = ents.device
+        tot = int(n_e.sum())
+        rows = torch.repeat_interleave(row_ptr[ents] - (torch.cumsum(n_e, 0) - n_e), n_e, output_size=tot)
+        rows = rows + torch.arange(tot, device=dev)
+        k0 = nip[rows]
+        nk = nip[rows + 1] - k0
+        nnz = int(nk.sum())
+        idx = torch.repeat_interleave(k0 - (torch.cumsum(nk, 0) - nk), nk, output_size=nnz)
+        idx = idx + torch.arange(nnz, device=dev)
+        c_lo = torch.repeat_interleave(torch.repeat_interleave(col_ptr[ents], n_e, output_size=tot), nk,
+                                       output_size=nnz)
+        c_hi = torch.repeat_interleave(torch.repeat_interleave(col_ptr[ents + 1], n_e, output_size=tot), nk,
+                                       output_size=nnz)
+        p = pos[idx]
+        if bool(((p < c_lo) | (p >= c_hi)).any()):
+            raise ValueError("FULL variance: an entry's column lies outside its entity's coefficient range")
+
+
+def var_normal(ents: torch.Tensor, n: int, row_ptr: torch.Tensor, col_ptr: torch.Tensor, csr, c: torch.Tensor,
+               lam: float, validated: bool = False) -> torch.Tensor:
+    """Primal normal matrices ``A [B, n, n] = lam I + X_e^T diag(c) X_e`` of the entities ``ents`` (``d_e <= n <=
+    VAR_MMAX``; rows / columns ``>= d_e``: identity) from the canonical block-diagonal CSR ``csr = (nip, pos, val)``
+    (int64 / int64 / fp64, strictly increasing columns inside a row) — ``var_normal_kernel``, one wave per entity.
+    ``c``: fp64 curvature per row. Device only; inputs are checked on the host first (:func:`check_var_class`)."""
+    lib = require_game_lib()
+    if not validated:
+        check_var_class(VAR_PRIMAL, n, ents, row_ptr, col_ptr, None, csr, c)
+    B = int(ents.numel())
+    A = torch.empty(B, n, n, dtype=torch.float64, device=ents.device)
+    if B:
+        nip, pos, val = csr
+        check(lib.pml_var_normal(B, int(n), ents.data_ptr(), row_ptr.data_ptr(), col_ptr.data_ptr(), nip.data_ptr(),
+                                 pos.data_ptr(), val.data_ptr(), c.data_ptr(), float(lam), A.data_ptr(),
+                                 stream_handle(ents.device)), "var_normal")
+    return A
+
+
+def var_scale_gram(K: torch.Tensor, ents: torch.Tensor, row_ptr: torch.Tensor, c: torch.Tensor, lam: float,
+                   validated: bool = False) -> torch.Tensor:
+    """In place: the Gram matrices ``K [B, n, n]`` (:func:`seg_gram`) become the row-space normal matrices
+    ``lam I + diag(s) K diag(s)``, ``s = sqrt(c)`` per row; rows / columns ``>= n_e``: identity
+    (``var_scale_gram_kernel``)."""
+    lib = require_game_lib()
+    B, n, n2 = K.shape
+    if n != n2 or K.dtype != torch.float64 or not K.is_contiguous() or B != ents.numel():
+        raise ValueError("var_scale_gram: K must be a contiguous fp64 [B, n, n] batch, one per entity")
+    if not validated:
+        check_var_class(VAR_ROW_SPACE, n, ents, row_ptr, row_ptr, None, None, c)
+    if B:
+        check(lib.pml_var_scale_gram(B, n, ents.data_ptr(), row_ptr.data_ptr(), c.data_ptr(), float(lam),
+                                     K.data_ptr(), stream_handle(K.device)), "var_scale_gram")
+    return K
+
+
+def chol_colnorm(mode: int, L: torch.Tensor, nv: torch.Tensor, ents: torch.Tensor, row_ptr: torch.Tensor,
+                 col_ptr: torch.Tensor, out: torch.Tensor, lam: float = 0.0, csr=None,
+                 c: Optional[torch.Tensor] = None, validated: bool = False) -> None:
+    """Variances from Cholesky factors (``chol_colnorm_kernel``): for the lower factors ``L [B, n, n]``
+    (:func:`batched_cholesky`; order ``nv[b] <= n <= VAR_MMAX``) of the entities ``ents``, writes into
+    ``out[col_ptr[e] + j]`` the squared norm of column j of ``G^-1 R``: ``mode = VAR_PRIMAL``: ``R = I``, the value
+    itself (``(H^-1)_jj``); ``mode = VAR_ROW_SPACE``: ``R = diag(sqrt c) X_e`` from the canonical CSR, ``(1 - q_j) /
+    lam``. Inputs are checked on the host first; a violated bound raises and nothing is launched."""
+    lib = require_game_lib()
+    B, n, n2 = L.shape
+    if n != n2 or L.dtype != torch.float64 or not L.is_contiguous() or B != ents.numel():
+        raise ValueError("chol_colnorm: L must be a contiguous fp64 [B, n, n] batch, one per entity")
+    if mode == VAR_ROW_SPACE and (csr is None or c is None or not lam > 0):
+        raise ValueError("chol_colnorm: the row-space route needs the CSR, the row curvature and lam > 0")
+    if not validated:
+        check_var_class(mode, n, ents, row_ptr, col_ptr, nv, csr if mode == VAR_ROW_SPACE else None,
+                        c if mode == VAR_ROW_SPACE else None, out)
+    if not B:
+        return
+    nip, pos, val = csr if mode == VAR_ROW_SPACE else (None, None, None)
+    p = lambda t: None if t is None else t.data_ptr()
+    check(lib.pml_chol_colnorm(int(mode), B, n, L.data_ptr(), nv.data_ptr(), ents.data_ptr(), row_ptr.data_ptr(),
+                               col_ptr.data_ptr(), p(nip), p(pos), p(val), p(c) if mode == VAR_ROW_SPACE else None,
+                               float(lam), out.data_ptr(), stream_handle(L.device)), "chol_colnorm")
 
 
 def downsample_weights(y: torch.Tensor, w0: torch.Tensor, rate: float, binary: bool, seed: int,

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from ..constants import EPSILON, TaskType
+from ..constants import EPSILON, TaskType, VarianceComputationType
 from ..function.losses import loss_for_task
 from ..function.objective import GLMObjective
 from ..models.glm import Coefficients, GeneralizedLinearModel, model_for_task
@@ -22,7 +22,16 @@ from .config import GLMOptimizationConfiguration, build_optimizer
 from .lbfgs import OWLQN
 
 
+FULL_VARIANCE_DMAX = 2048      # FULL variances of one GLM: the dense D x D Hessian is built from D products
+
+
 class GLMOptimizationProblem:
+    """``compute_variance``: a :class:`VarianceComputationType` or the legacy boolean (True = SIMPLE). FULL builds the
+    dense Hessian from ``D`` Hessian-vector products of the objective on unit vectors (which all-reduce under a
+    process group and fold the normalization as every other product does) and inverts it with torch; it is
+    supported for ``D <= FULL_VARIANCE_DMAX`` and not with feature-sharded optimizer state (checked by
+    :meth:`check_full_variance` as soon as the dimension is known)."""
+
     def __init__(self, config: GLMOptimizationConfiguration, task, normalization: Optional[NormalizationContext] = None,
                  compute_variance: bool = False, track_state: bool = True, feature_sharded: bool = False):
         self.config = config
@@ -33,7 +42,10 @@ class GLMOptimizationProblem:
         self.task = TaskType.parse(task)
         self.loss = loss_for_task(self.task)
         self.normalization = normalization or no_normalization()
-        self.compute_variance = compute_variance
+        self.variance_type = VarianceComputationType.parse(compute_variance)
+        self.compute_variance = self.variance_type != VarianceComputationType.NONE
+        if self.variance_type == VarianceComputationType.FULL and feature_sharded:
+            raise ValueError("FULL variances are not supported with feature-sharded optimizer state")
         self.track_state = track_state
         reg = config.regularization_context
         lam = config.regularization_weight
@@ -47,6 +59,27 @@ class GLMOptimizationProblem:
         if isinstance(self.optimizer, OWLQN):
             self.optimizer.l1_weight = reg.l1_weight(lam)
 
+    def check_full_variance(self, dim: int, name: str = "fixed effect"):
+        """Raise before any training when FULL variances cannot be computed for a problem of ``dim`` coefficients."""
+        if (self.variance_type == VarianceComputationType.FULL and self.loss.twice_differentiable
+                and int(dim) > FULL_VARIANCE_DMAX):
+            raise ValueError(f"coordinate {name}: FULL variances need D <= {FULL_VARIANCE_DMAX}, got D = {int(dim)}")
+
+    def _variances(self, data, w_t: torch.Tensor) -> torch.Tensor:
+        """Transformed-space variances at ``w_t``: SIMPLE = 1 / (H_jj + EPSILON), FULL = (H^-1)_jj."""
+        if self.variance_type != VarianceComputationType.FULL:
+            return 1.0 / (self.objective.hessian_diagonal(data, w_t) + EPSILON)
+        from .variance import hessian_full_variance
+        d = w_t.numel()
+        self.check_full_variance(d)
+        H = torch.empty(d, d, dtype=torch.float64, device=w_t.device)
+        unit = torch.zeros(d, dtype=torch.float64, device=w_t.device)
+        for j in range(d):
+            unit[j] = 1.0
+            H[:, j] = self.objective.hessian_vector(data, w_t, unit).to(H)
+            unit[j] = 0.0
+        return hessian_full_variance(0.5 * (H + H.T)).to(w_t.device)
+
     @property
     def tracker(self):
         return self.optimizer.tracker
@@ -58,6 +91,7 @@ class GLMOptimizationProblem:
             ) -> GeneralizedLinearModel:
         dev = self._device_of(data)
         d = dim if dim is not None else data.dim
+        self.check_full_variance(d)
         w0 = (initial.coefficients.means.to(dev, torch.float64) if initial is not None
               else torch.zeros(d, dtype=torch.float64, device=dev))
         if self.feature_sharded:
@@ -70,8 +104,7 @@ class GLMOptimizationProblem:
             w_t, _ = self.optimizer.optimize(self.objective, data, w0)
         variances = None
         if self.compute_variance and self.loss.twice_differentiable:
-            hd = self.objective.hessian_diagonal(data, w_t)
-            variances = self.normalization.model_to_original_space(1.0 / (hd + EPSILON))
+            variances = self.normalization.model_to_original_space(self._variances(data, w_t))
         means = self.normalization.model_to_original_space(w_t)
         model = model_for_task(self.task, Coefficients(means.detach(), None if variances is None else variances))
         model.validate_coefficients()
