@@ -95,7 +95,11 @@ class Coordinate:
 class FixedEffectCoordinate(Coordinate):
     def __init__(self, coordinate_id: str, data: GameData, data_config: FixedEffectDataConfiguration,
                  opt_config: GLMOptimizationConfiguration, task, normalization: Optional[NormalizationContext] = None,
-                 compute_variance: bool = False, device=None, precision: str = "f64", local_rows=None):
+                 compute_variance: bool = False, device=None, precision: str = "f64", local_rows=None,
+                 prior: Optional[FixedEffectModel] = None):
+        """``prior``: yesterday's model of this coordinate as a Gaussian prior (incremental training): its means and
+        variances (1 without variances) replace the L2 term by ``lambda/2 sum (w_j - mu_j)^2 / sigma_j^2``
+        (``GLMOptimizationProblem``); the prior margins ``X mu`` join the base offsets here, once."""
         self.coordinate_id = coordinate_id
         self.data = data
         self.shard_id = data_config.feature_shard_id
@@ -135,12 +139,28 @@ class FixedEffectCoordinate(Coordinate):
         self.variance_type = VarianceComputationType.parse(compute_variance)
         self.compute_variance = self.variance_type != VarianceComputationType.NONE
         self.normalization = normalization
-        self.set_config(opt_config)
+        self.prior = None
+        if prior is not None:
+            co = prior.glm.coefficients
+            mu = co.means.detach().to("cpu", torch.float64)
+            if mu.numel() != self.dim:
+                raise ValueError(f"coordinate {coordinate_id}: prior model has {mu.numel()} coefficients, the shard "
+                                 f"{self.dim}")
+            var = torch.ones_like(mu) if co.variances is None else co.variances.detach().to("cpu", torch.float64)
+            if not (bool(torch.isfinite(mu).all()) and bool(torch.isfinite(var).all())):
+                raise ValueError(f"coordinate {coordinate_id}: prior model has non-finite means or variances")
+            self.prior = (mu, var.clamp(min=EPSILON).sqrt())
+        self.set_config(opt_config)                                   # raises on what a prior cannot combine with
+        if self.prior is not None:
+            with phase(f"FE {coordinate_id} build: prior margins"):
+                xm = gd.margins(self.prior[0].to(gd.device)).detach().to("cpu", torch.float64).numpy()
+                self.base_offsets = self.base_offsets + xm[: len(self.base_offsets)]
         self.last_tracker = None
 
     def set_config(self, opt_config: GLMOptimizationConfiguration):
         self.opt_config = opt_config
-        self.problem = GLMOptimizationProblem(opt_config, self.task, self.normalization, self.variance_type)
+        self.problem = GLMOptimizationProblem(opt_config, self.task, self.normalization, self.variance_type,
+                                              prior=self.prior, name=self.coordinate_id)
         self.problem.check_full_variance(self.dim, self.coordinate_id)     # before any training
         rate = opt_config.down_sampling_rate
         self.sampler = down_sampler_for_task(self.task, rate) if rate < 1.0 else None
@@ -263,19 +283,34 @@ class RandomEffectCoordinate(Coordinate):
 
     def __init__(self, coordinate_id: str, data: GameData, data_config: RandomEffectDataConfiguration,
                  opt_config: GLMOptimizationConfiguration, task, compute_variance: bool = False, device=None,
-                 dtype=torch.float64, entity_subset=None, layout: str = "auto"):
+                 dtype=torch.float64, entity_subset=None, layout: str = "auto",
+                 prior: Optional[RandomEffectModel] = None):
+        """``prior``: yesterday's model of this coordinate as a Gaussian prior (incremental training): the penalty
+        becomes ``lambda/2 sum_j (w_j - mu_j)^2 / sigma_j^2`` per entity and feature (``mu = 0, sigma^2 = 1`` where
+        the prior model has no coefficient). The dataset folds it into the data once (``PriorFold``): inside this
+        coordinate every solver state is ``v = (w - mu) / sigma`` under plain L2, outside it (models, scores,
+        warm starts) everything stays in the original space."""
         self.coordinate_id = coordinate_id
         self.data = data
         self.data_config = data_config
         self.task = TaskType.parse(task)
         self.loss = loss_for_task(self.task)
         self.device = torch.device(device) if device is not None else default_device()
+        self.has_prior = prior is not None
+        if self.has_prior:
+            if data_config.projector_type.kind.value == "RANDOM":
+                raise ValueError(f"coordinate {coordinate_id}: a prior model cannot be combined with the RANDOM "
+                                 f"projector")
+            self._check_prior_config(opt_config)                     # before the dataset is built
         with phase(f"RE {coordinate_id} build: dataset"):
             self.dataset = RandomEffectDataset(data, data_config, self.device, dtype, entity_subset=entity_subset,
-                                               layout=layout)
+                                               layout=layout, prior=prior)
         self.variance_type = VarianceComputationType.parse(compute_variance)
         self.compute_variance = self.variance_type != VarianceComputationType.NONE
         self.base_offsets = torch.from_numpy(data.offsets).to(self.device)
+        if self.has_prior:
+            # the prior model's score on the active rows, once: the solvers see X (w - mu)
+            self.base_offsets = self.base_offsets + self.dataset.prior.row_margins.to(self.device)
         self.set_config(opt_config)
         self._W = {}  # projected-space warm-start state per bucket
         self._returned = None  # the model object the last update returned (its solver state is in _W / _rs)
@@ -316,8 +351,19 @@ class RandomEffectCoordinate(Coordinate):
     def _defer_stats(self, iters: torch.Tensor, reasons: torch.Tensor, act: torch.Tensor, seconds: float):
         self.__dict__["_stats_thunk"] = lambda: random_effect_tracker_stats(iters[act], reasons[act], seconds)
 
+    def _check_prior_config(self, opt_config: GLMOptimizationConfiguration):
+        """What a prior cannot be combined with (ValueError naming the coordinate, before any training)."""
+        rt = opt_config.regularization_context.regularization_type
+        if rt in (RegularizationType.L1, RegularizationType.ELASTIC_NET):
+            raise ValueError(f"coordinate {self.coordinate_id}: {rt.value} regularization cannot be combined with a "
+                             f"prior model (the L1 term lives on w, the solvers on (w - mu) / sigma)")
+        if opt_config.optimizer_config.constraint_map:
+            raise ValueError(f"coordinate {self.coordinate_id}: box constraints cannot be combined with a prior model")
+
     def set_config(self, opt_config: GLMOptimizationConfiguration):
         rt = opt_config.regularization_context.regularization_type
+        if getattr(self, "has_prior", False):
+            self._check_prior_config(opt_config)
         if opt_config.optimizer_config.optimizer_type == OptimizerType.TRON and rt in (
                 RegularizationType.L1, RegularizationType.ELASTIC_NET):
             raise ValueError("TRON optimizer incompatible with L1 regularization")
@@ -332,6 +378,7 @@ class RandomEffectCoordinate(Coordinate):
         """Forget cached solver state (bucket W, segmented W, row-space beta, lazy primal model)."""
         self._W = {}
         self._returned = None
+        self._v_sq = None
         if getattr(self, "_rs", None) is not None:
             self._rs.beta = None
         comps = getattr(self, "_comps", None)
@@ -368,6 +415,8 @@ class RandomEffectCoordinate(Coordinate):
             Wn = np.zeros((B, d))
             Wn[np.asarray(b_idx, dtype=np.int64), np.asarray(c_idx, dtype=np.int64)] = vals
             W = torch.from_numpy(Wn).to(dev, dt)
+            if bucket.mu is not None:                  # original space -> the solver's v = (w - mu) / sigma
+                W = (W - bucket.mu) / bucket.sigma
         return W
 
     def update_model(self, model: Optional[RandomEffectModel], partial_score: Optional[torch.Tensor] = None):
@@ -391,6 +440,7 @@ class RandomEffectCoordinate(Coordinate):
         iters, reasons = [], []
         self.last_variance_routes = {}
         t_start = time.time()
+        v_sq = 0.0
         for b, bucket in enumerate(ds.buckets):
             O = ds.bucket_offsets(bucket, offs)
             bd = BatchedGLMData(bucket.X, bucket.y, O, bucket.w)
@@ -412,6 +462,10 @@ class RandomEffectCoordinate(Coordinate):
             if self.compute_variance and self.loss.twice_differentiable:
                 var = (self._full_variance_dense(bd, W, l2) if self._full_var else
                        1.0 / (bd.hdiag(self.loss, W, l2) + EPSILON))
+            if bucket.mu is not None:
+                v_sq = v_sq + float(W.to(torch.float64).square().sum())
+                W = bucket.mu + bucket.sigma * W                       # w = mu + sigma v, var_w = sigma^2 var_v
+                var = None if var is None else bucket.sigma.square() * var
             k, v, vv = self._to_original(bucket, W, var)
             keys.append(k)
             vals.append(v)
@@ -423,8 +477,10 @@ class RandomEffectCoordinate(Coordinate):
         keys = np.concatenate(keys) if keys else np.zeros(0, np.int64)
         vals = np.concatenate(vals) if vals else np.zeros(0)
         variances = np.concatenate(vars_) if vars_ else None
-        return RandomEffectModel(self.data_config.random_effect_type, self.data_config.feature_shard_id, self.task,
-                                 ds.entity_ids, ds.dim, keys, vals, variances)
+        out = RandomEffectModel(self.data_config.random_effect_type, self.data_config.feature_shard_id, self.task,
+                                ds.entity_ids, ds.dim, keys, vals, variances)
+        self._v_sq = (out, v_sq)
+        return out
 
     @property
     def _full_var(self) -> bool:
@@ -572,8 +628,10 @@ class RandomEffectCoordinate(Coordinate):
             self._defer_stats(n_iter, n_reason, act, time.time() - t_start)
             sum_sq = float(torch.linalg.vector_norm(torch.where(rs.valid, beta, torch.zeros_like(beta)))) ** 2
             out = RandomEffectModel(self.data_config.random_effect_type, self.data_config.feature_shard_id, self.task,
-                                    ds.entity_ids, ds.dim, ds.projection_keys_t, self._lazy_W, None, sum_sq=sum_sq)
+                                    ds.entity_ids, ds.dim, ds.projection_keys_t, self._original_thunk(self._lazy_W),
+                                    None, sum_sq=sum_sq)
             self._last = (out, None)
+            self._v_sq = (out, sum_sq)
             return out
         if frozen is not None:
             with Timed(f"RE {self.coordinate_id}: row-space -> primal", log, logging.DEBUG):
@@ -596,9 +654,12 @@ class RandomEffectCoordinate(Coordinate):
         # the model keeps the projected keys (entity * dim + feature, sorted, aligned with W) without compaction:
         # W is dense in the projected space, and zeros are harmless (dropped at save, <1e-4 as in the reference);
         # compacting 1.25e9 coefficients per update was ~40 GB of traffic at config 5
+        v_sq = float(W.square().sum()) if self.has_prior else None
+        W, var = self._to_original_segmented(W, var)
         out = RandomEffectModel(self.data_config.random_effect_type, self.data_config.feature_shard_id, self.task,
                                 ds.entity_ids, ds.dim, ds.projection_keys_t, W, var)
         self._last = (out, res.W)
+        self._v_sq = None if v_sq is None else (out, v_sq)
         return out
 
     def _components(self, l1: float, oc):
@@ -807,14 +868,16 @@ class RandomEffectCoordinate(Coordinate):
             W = primal()
             var = (self._full_variance_segmented(W, l2) if self._full_var else
                    1.0 / (seg.hdiag(self.loss, W, l2) + EPSILON))
+            W, var = self._to_original_segmented(W, var)
             out = RandomEffectModel(self.data_config.random_effect_type, self.data_config.feature_shard_id,
                                     self.task, ds.entity_ids, ds.dim, ds.projection_keys_t, W, var)
         else:
             self._lazy_W = primal
             out = RandomEffectModel(self.data_config.random_effect_type, self.data_config.feature_shard_id,
-                                    self.task, ds.entity_ids, ds.dim, ds.projection_keys_t, primal, None,
-                                    sum_sq=float(sum_sq))
+                                    self.task, ds.entity_ids, ds.dim, ds.projection_keys_t,
+                                    self._original_thunk(primal), None, sum_sq=float(sum_sq))
         self._last = (out, None)
+        self._v_sq = (out, float(sum_sq)) if self.has_prior else None
         return out
 
     def _sub_inputs(self, sub, seg, W0) -> torch.Tensor:
@@ -893,7 +956,25 @@ class RandomEffectCoordinate(Coordinate):
         mk, mv = model.tensors(dev)
         pos = torch.searchsorted(mk, k).clamp(max=mk.numel() - 1)
         hit = (mk[pos] == k) & (mi >= 0)
-        return torch.where(hit, mv[pos], torch.zeros_like(mv[pos]))
+        W = torch.where(hit, mv[pos], torch.zeros_like(mv[pos]))
+        pr = ds.prior
+        if pr is not None:                             # original space -> the solver's v = (w - mu) / sigma
+            W = (W - pr.mu) / pr.sigma
+        return W
+
+    def _to_original_segmented(self, V: torch.Tensor, var: Optional[torch.Tensor] = None):
+        """Packed solver-space coefficients (and variances) as original-space ones: ``w = mu + sigma v``, ``var_w =
+        sigma^2 var_v`` (exact for SIMPLE and FULL: ``H_w^-1 = S H_v^-1 S``). The inputs themselves without a prior."""
+        pr = self.dataset.prior
+        if pr is None:
+            return V, var
+        return pr.mu + pr.sigma * V, (None if var is None else pr.sigma.square() * var)
+
+    def _original_thunk(self, primal):
+        """The lazy model's coefficient thunk in the original space (``primal`` itself without a prior)."""
+        if self.dataset.prior is None:
+            return primal
+        return lambda: self._to_original_segmented(primal())[0]
 
     def _to_original(self, bucket, W: torch.Tensor, var: Optional[torch.Tensor]):
         ds = self.dataset
@@ -943,6 +1024,8 @@ class RandomEffectCoordinate(Coordinate):
             else:
                 out = torch.zeros(self.data.n_rows, dtype=torch.float64, device=z.device)
                 out[ds.seg_rows] = z
+            if ds.prior is not None:
+                out += ds.prior.row_margins.to(out.device)       # the solver margins are X (w - mu) on active rows
             if len(ds.passive_rows):
                 pm = np.zeros(self.data.n_rows, dtype=bool)
                 pm[ds.passive_rows] = True
@@ -953,8 +1036,40 @@ class RandomEffectCoordinate(Coordinate):
     def regularization_term_value(self, model: RandomEffectModel) -> float:
         reg, lam = self.opt_config.regularization_context, self.opt_config.regularization_weight
         l1w = reg.l1_weight(lam)
+        if self.has_prior:
+            # lambda/2 sum (w - mu)^2 / sigma^2 = lambda/2 ||v||^2 (no L1 with a prior)
+            return 0.5 * reg.l2_weight(lam) * self._prior_sum_sq(model)
         a, q = model.sum_abs_and_sq(need_abs=l1w != 0)
         return (l1w * a if l1w != 0 else 0.0) + 0.5 * reg.l2_weight(lam) * q
+
+
+    def _prior_sum_sq(self, model: RandomEffectModel) -> float:
+        """``sum (w - mu)^2 / sigma^2`` of ``model`` over this coordinate's coefficients: kept from the solve for the
+        model returned last, mapped from the model's coefficients otherwise."""
+        kept = getattr(self, "_v_sq", None)
+        if kept is not None and kept[0] is model:
+            return float(kept[1])
+        ds = self.dataset
+        if ds.layout == "segmented":
+            pr = ds.prior
+            if model.nnz == 0:
+                return float((pr.mu / pr.sigma).square().sum())
+            saved, self._W = self._W, {}
+            try:
+                return float(self._warm_start_segmented(model).square().sum())
+            finally:
+                self._W = saved
+        saved, self._W = self._W, {}
+        try:
+            total = 0.0
+            for b, bucket in enumerate(ds.buckets):
+                V = self._warm_start(b, bucket, model)
+                if model.nnz == 0:
+                    V = -bucket.mu / bucket.sigma
+                total += float(V.to(torch.float64).square().sum())
+            return total
+        finally:
+            self._W = saved
 
 
 class ShardedRandomEffectCoordinate(Coordinate):
@@ -970,7 +1085,9 @@ class ShardedRandomEffectCoordinate(Coordinate):
 
     def __init__(self, coordinate_id: str, data: GameData, data_config: RandomEffectDataConfiguration,
                  opt_config: GLMOptimizationConfiguration, task, compute_variance: bool = False, device=None,
-                 dtype=torch.float64):
+                 dtype=torch.float64, prior: Optional[RandomEffectModel] = None):
+        """``prior``: passed to the inner coordinate (the loaded model is whole on every rank; the lookup is by
+        entity id, so each rank folds the priors of the entities it owns)."""
         from ..parallel.sharding import EntityPartitioner, RowRouter, entity_keys
         self.coordinate_id = coordinate_id
         self.data_config = data_config
@@ -997,7 +1114,7 @@ class ShardedRandomEffectCoordinate(Coordinate):
             self.route_times["partition"] = time.perf_counter() - t0
             self.recv_data = self._route(data, self.router, ids, self.route_times)
         self.inner = RandomEffectCoordinate(coordinate_id, self.recv_data, data_config, opt_config, task,
-                                            compute_variance, device, dtype)
+                                            compute_variance, device, dtype, prior=prior)
         self._val_cache = {}
 
     def _sync(self):

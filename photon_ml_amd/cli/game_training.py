@@ -117,6 +117,8 @@ class _TrainingParser(argparse.ArgumentParser):
         if t is not None and given and bool(ns.compute_variance) != (t != VarianceComputationType.NONE.value):
             self.error(f"--compute-variance {str(bool(ns.compute_variance)).lower()} contradicts "
                        f"--variance-computation-type {t}")
+        if getattr(ns, "incremental_training", False) and not getattr(ns, "model_input_directory", None):
+            self.error("--incremental-training true requires --model-input-directory (the prior model)")
         return ns
 
 
@@ -168,6 +170,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--checkpoint-directory", help="save coordinate-descent state after every coordinate update")
     p.add_argument("--model-input-directory",
                    help="initialise training from a saved GAME model directory (e.g. a previous run's best/)")
+    p.add_argument("--incremental-training", type=parse_bool, default=False,
+                   help="use the model of --model-input-directory as a Gaussian prior as well as the starting point: "
+                        "each coordinate's L2 term becomes lambda/2 sum (w - mean)^2 / variance with that model's "
+                        "means and variances (variance 1 where it has none)")
     p.add_argument("--resume", type=parse_bool, default=False,
                    help="continue an interrupted run from --checkpoint-directory (the output directory is kept)")
     return p
@@ -349,7 +355,10 @@ class GameTrainingDriver(GameDriverBase):
         est.coordinates_built_callback = coordinates_built
         if a.model_input_directory:
             from ..io.model_io import load_game_model
-            est.set_initial_model(load_game_model(a.model_input_directory, maps))
+            loaded = load_game_model(a.model_input_directory, maps)
+            est.set_initial_model(loaded)
+            if a.incremental_training:
+                est.set_prior_model(loaded)
         if a.evaluators:
             est.set_validation_evaluators(split_list(a.evaluators))
         if a.checkpoint_directory:

@@ -113,10 +113,54 @@ class SegmentSubset:
 class Bucket:
     entities: np.ndarray      # entity indices in this bucket [B]
     rows: torch.Tensor        # [B, n] global sample index of each slot, -1 for padding
-    X: torch.Tensor           # [B, n, d] projected features
+    X: torch.Tensor           # [B, n, d] projected features (column-scaled by the prior sigma when there is a prior)
     y: torch.Tensor           # [B, n]
     w: torch.Tensor           # [B, n] (0 on padding, x reservoir multiplier)
     d_local: np.ndarray       # projected dim per entity
+    mu: Optional[torch.Tensor] = None      # [B, d] prior means (0 on padding), None without a prior
+    sigma: Optional[torch.Tensor] = None   # [B, d] prior standard deviations (1 on padding)
+
+
+@dataclass
+class PriorFold:
+    """A Gaussian prior folded into a random-effect dataset (incremental training). With ``w = mu + sigma v`` the
+    penalty ``lambda/2 sum (w - mu)^2 / sigma^2`` is plain L2 on ``v`` over column-scaled data ``X diag(sigma)`` with
+    the offsets shifted by ``X mu``: the dataset holds the scaled data, the solvers see ``v``, and the coordinate
+    maps ``v <-> w`` at its boundary. ``mu`` / ``sigma``: per packed projected coefficient (segmented layout; the
+    dense layout keeps them per bucket). ``row_margins``: ``x_i . mu_{e(i)}`` of every active row in sample order
+    (0 elsewhere), on the dataset's device."""
+    mu: Optional[torch.Tensor]
+    sigma: Optional[torch.Tensor]
+    row_margins: torch.Tensor
+
+
+def prior_lookup(prior, entity_ids: np.ndarray, dim: int, col_entity: torch.Tensor, col_feature: torch.Tensor):
+    """``(mu, sigma)`` of the coefficients ``(col_entity, col_feature)`` (dataset entity index, original feature)
+    in the prior random-effect model, on the device of ``col_entity``. A coefficient the prior model does not hold (a
+    new entity, a feature the entity never had or that was dropped at save) gets ``mu = 0, sigma = 1``: plain L2. A
+    model without variances gives ``sigma = 1`` everywhere. Variances below ``EPSILON`` are raised to it; a
+    non-finite prior value raises."""
+    dev = col_entity.device
+    if int(prior.dim) != int(dim):
+        raise ValueError(f"prior model of random effect {prior.random_effect_type} has {prior.dim} features, the "
+                         f"data {dim}")
+    n = col_entity.numel()
+    mu = torch.zeros(n, dtype=torch.float64, device=dev)
+    var = torch.ones(n, dtype=torch.float64, device=dev)
+    if n == 0 or prior.nnz == 0:
+        return mu, var
+    mi = torch.from_numpy(prior.entity_index(entity_ids).astype(np.int64)).to(dev)[col_entity]
+    k = mi * int(dim) + col_feature
+    mk, mv = prior.tensors(dev)
+    pvar = prior.variance_tensor(dev)
+    pos = torch.searchsorted(mk, k).clamp(max=mk.numel() - 1)
+    hit = (mk[pos] == k) & (mi >= 0)
+    mu = torch.where(hit, mv[pos], mu)
+    if pvar is not None:
+        var = torch.where(hit, pvar[pos], var)
+    if not (bool(torch.isfinite(mu).all()) and bool(torch.isfinite(var).all())):
+        raise ValueError(f"prior model of random effect {prior.random_effect_type} has non-finite means or variances")
+    return mu, var.clamp(min=EPSILON).sqrt()
 
 
 def sorted_factors(codes: np.ndarray, table) -> Optional[tuple]:
@@ -176,13 +220,21 @@ class RandomEffectDataset:
 
     def __init__(self, data: GameData, config: RandomEffectDataConfiguration, device="cpu",
                  dtype=torch.float64, bucket_elems: int = 1 << 24, entity_subset: Optional[np.ndarray] = None,
-                 layout: str = "auto"):
-        """``layout``: ``dense`` = size buckets of padded ``[B, n, d]`` problems (batched GEMMs); ``segmented`` =
+                 layout: str = "auto", prior=None):
+        """``prior``: a :class:`RandomEffectModel` whose means / variances become a Gaussian prior folded into the
+        data once, here (:class:`PriorFold`, kept as ``self.prior``; None: plain L2).
+
+        ``layout``: ``dense`` = size buckets of padded ``[B, n, d]`` problems (batched GEMMs); ``segmented`` =
         one block-diagonal sparse GLM over all entities (INDEX_MAP projection only; the GLM kernels do the
         products, no padding). ``auto`` = segmented for INDEX_MAP on a GPU, dense otherwise."""
         self.config = config
         self.device = torch.device(device)
         self.dtype = dtype
+        self.prior = None
+        self._prior_model = prior
+        if prior is not None and config.projector_type.kind == ProjectorKind.RANDOM:
+            raise ValueError("a prior model cannot be combined with the RANDOM projector (the prior lives on "
+                             "original-space coefficients)")
         re_type, shard_id = config.random_effect_type, config.feature_shard_id
         x = data.shard(shard_id)
         # device copy of the shard started by GameData.prefetch_shard (used by the segmented device build below when
@@ -420,6 +472,7 @@ class RandomEffectDataset:
         starts = np.zeros(n_ent + 1, dtype=np.int64)
         starts[1:] = np.cumsum(n_act)
         out = []
+        row_margins = np.zeros(self.n_rows)            # prior margins of the active rows (with a prior model)
         for be in buckets_e:
             be = np.asarray(be, dtype=np.int64)
             B = len(be)
@@ -432,6 +485,11 @@ class RandomEffectDataset:
             rr, cc, vv = self._project_rows(xr, ea[loc_rows])
             X = np.zeros((B, nmax, dmax))
             X[slot_b[rr], slot_r[rr], cc] = vv
+            mu_b = sg_b = None
+            if self._prior_model is not None:
+                mu_b, sg_b = self._bucket_prior(be, d_local, dmax)
+                row_margins[active_rows[loc_rows]] = np.einsum("bnd,bd->bn", X, mu_b)[slot_b, slot_r]
+                X = X * sg_b[:, None, :]
             rows = np.full((B, nmax), -1, dtype=np.int64)
             rows[slot_b, slot_r] = active_rows[loc_rows]
             Y = np.zeros((B, nmax))
@@ -440,8 +498,30 @@ class RandomEffectDataset:
             W[slot_b, slot_r] = wts[active_rows[loc_rows]]
             dev, dt = self.device, self.dtype
             out.append(Bucket(be, torch.from_numpy(rows).to(dev), torch.from_numpy(X).to(dev, dt),
-                              torch.from_numpy(Y).to(dev, dt), torch.from_numpy(W).to(dev, dt), d_local[be]))
+                              torch.from_numpy(Y).to(dev, dt), torch.from_numpy(W).to(dev, dt), d_local[be],
+                              None if mu_b is None else torch.from_numpy(mu_b).to(dev, dt),
+                              None if sg_b is None else torch.from_numpy(sg_b).to(dev, dt)))
+        if self._prior_model is not None:
+            self.prior = PriorFold(None, None, torch.from_numpy(row_margins).to(dev))
         return out
+
+    def _bucket_prior(self, be: np.ndarray, d_local: np.ndarray, dmax: int):
+        """``(mu, sigma)`` [B, dmax] of a dense bucket's projected coefficients (0 / 1 on padding columns)."""
+        dl = d_local[be]
+        b_idx = np.repeat(np.arange(len(be)), dl)
+        c_idx = np.concatenate([np.arange(x) for x in dl]) if len(be) else np.zeros(0, np.int64)
+        if self.projector_type.kind == ProjectorKind.INDEX_MAP:
+            ptr, feat = self.projection.ptr, self.projection.feat
+            gf = np.concatenate([feat[ptr[e]:ptr[e + 1]] for e in be]) if len(be) else np.zeros(0, np.int64)
+        else:
+            gf = c_idx
+        mu, sigma = prior_lookup(self._prior_model, self.entity_ids, self.dim,
+                                 torch.from_numpy(np.repeat(be, dl).astype(np.int64)),
+                                 torch.from_numpy(np.asarray(gf, dtype=np.int64)))
+        mu_b, sg_b = np.zeros((len(be), dmax)), np.ones((len(be), dmax))
+        mu_b[b_idx, c_idx] = mu.numpy()
+        sg_b[b_idx, c_idx] = sigma.numpy()
+        return mu_b, sg_b
 
     def _make_segmented(self, xa, ea, active_rows, y, wts, n_ent):
         from ..ops.backend import make_glm_data
@@ -453,13 +533,24 @@ class RandomEffectDataset:
         d_total = int(self.projection.ptr[-1])
         x_seg = sp.csr_matrix((xs.data, (xs.row, pos)), shape=(len(order), max(d_total, 1)))
         rows = active_rows[order]
+        col_entity = np.repeat(np.arange(n_ent, dtype=np.int64), np.diff(self.projection.ptr))
+        if self._prior_model is not None:
+            # the same fold as the device build (ops.native.prior_fold, its torch definition here)
+            from ..ops.native import prior_fold
+            mu, sigma = prior_lookup(self._prior_model, self.entity_ids, self.dim, torch.from_numpy(col_entity),
+                                     torch.from_numpy(self.projection.keys % self.dim))
+            vt = torch.from_numpy(x_seg.data.astype(np.float64))
+            m = prior_fold(torch.from_numpy(x_seg.indptr.astype(np.int64)),
+                           torch.from_numpy(x_seg.indices.astype(np.int64)), vt, mu, sigma)
+            x_seg = sp.csr_matrix((vt.numpy(), x_seg.indices, x_seg.indptr), shape=x_seg.shape)
+            rm = torch.zeros(self.n_rows, dtype=torch.float64).index_copy_(0, torch.from_numpy(rows), m)
+            self.prior = PriorFold(mu.to(self.device), sigma.to(self.device), rm.to(self.device))
         yy = np.asarray(y, dtype=np.float64)[rows]
         ww = np.asarray(wts, dtype=np.float64)[rows]
         glm = make_glm_data(LabeledData(x_seg, yy, np.zeros(len(rows)), ww), self.device, "f64", col_windows=True)
         dev = glm.device
         self._seg_csr = (torch.from_numpy(x_seg.indptr.astype(np.int64)), torch.from_numpy(
             x_seg.indices.astype(np.int64)), torch.from_numpy(x_seg.data.astype(np.float64)))
-        col_entity = np.repeat(np.arange(n_ent, dtype=np.int64), np.diff(self.projection.ptr))
         self.seg_rows = torch.from_numpy(rows).to(dev)
         self.projection_keys_t = torch.from_numpy(self.projection.keys).to(dev)
         self.col_entity_t = torch.from_numpy(col_entity).to(dev)
@@ -532,6 +623,17 @@ class RandomEffectDataset:
         del key
         d_total = int(ukeys.numel())
         rows_t = torch.from_numpy(active_rows.astype(np.int64)).to(dev)[order]
+        if self._prior_model is not None:
+            # the one narrow point both the solver setup (_seg_csr) and the tiled layout (build_glm) derive from:
+            # prior margins from the original values, then the values scaled in place (val is a fresh gather;
+            # a second copy would double 8 B per non-zero)
+            from ..ops.native import prior_fold
+            with phase("RE segmented: prior fold"):
+                mu, sigma = prior_lookup(self._prior_model, self.entity_ids, D, ukeys // D, ukeys % D)
+                val = val.to(torch.float64).contiguous()
+                m = prior_fold(nip, pos.contiguous(), val, mu, sigma)
+                rm = torch.zeros(self.n_rows, dtype=torch.float64, device=dev).index_copy_(0, rows_t, m)
+                self.prior = PriorFold(mu, sigma, rm)
         yy = torch.from_numpy(np.asarray(y, dtype=np.float64)).to(dev)[rows_t]
         ww = torch.from_numpy(np.asarray(wts, dtype=np.float64)).to(dev)[rows_t]
         sort_phase.__exit__(None, None, None)

@@ -76,6 +76,7 @@ class GameEstimator:
         self.history: List[list] = []
         self.checkpoint_directory: Optional[str] = None
         self.resume = False
+        self.prior_model: Optional[GameModel] = None
 
     # fluent setters mirroring Spark ML Params ------------------------------------------------------------
     def set_training_task(self, t):
@@ -175,6 +176,24 @@ class GameEstimator:
         self.initial_model = model
         return self
 
+    def set_prior_model(self, model: Optional[GameModel]):
+        """Incremental training: use a saved model (e.g. ``load_game_model`` of yesterday's run, with variances) as a
+        Gaussian prior. Every coordinate the model holds trains with ``lambda/2 sum_j (w_j - mu_j)^2 / sigma_j^2`` in
+        place of its L2 term, ``mu`` / ``sigma^2`` the prior's means / variances (per entity and feature for a random
+        effect); a coefficient without a prior (a new entity or feature, a model saved without variances) keeps ``mu
+        = 0`` resp. ``sigma^2 = 1``, i.e. plain L2, as do coordinates absent from the model. Separate from
+        :meth:`set_initial_model`, which only chooses the starting point. Entities present only in the prior model
+        are not carried into the trained model, and the prior term has no weight of its own beyond ``lambda``."""
+        self.prior_model = model
+        return self
+
+    def _prior_for(self, cid: str, random_effect: bool):
+        from ..models.game import FixedEffectModel, RandomEffectModel
+        m = None if self.prior_model is None else self.prior_model.get(cid)
+        if m is not None and not isinstance(m, RandomEffectModel if random_effect else FixedEffectModel):
+            raise ValueError(f"coordinate {cid}: the prior model holds a {type(m).__name__} for it")
+        return m
+
     def set_checkpoint_directory(self, directory: Optional[str], resume: bool = False):
         """Checkpoint coordinate descent after every coordinate update (one state file per configuration and
         rank); with ``resume`` an interrupted fit continues where it stopped (see utils/checkpoint.py)."""
@@ -218,12 +237,18 @@ class GameEstimator:
             oc = first_cfg[cid]
             if isinstance(dc, RandomEffectDataConfiguration):
                 cls = ShardedRandomEffectCoordinate if is_dist() else RandomEffectCoordinate
-                coords[cid] = cls(cid, data, dc, oc, self.training_task, self.variance_computation_type, self.device)
+                coords[cid] = cls(cid, data, dc, oc, self.training_task, self.variance_computation_type, self.device,
+                                  prior=self._prior_for(cid, True))
             else:
                 explicit = self.coordinate_normalization_contexts.get(cid)
+                prior = self._prior_for(cid, False)
+                if prior is not None and explicit is None and self.normalization_type != NormalizationType.NONE:
+                    raise ValueError(f"coordinate {cid}: {self.normalization_type.value} normalization cannot be "
+                                     f"combined with a prior model on the same coordinate (the two transforms are not "
+                                     f"composed)")
                 co = coords[cid] = FixedEffectCoordinate(cid, data, dc, oc, self.training_task, explicit,
                                                          self.variance_computation_type, self.device,
-                                                         self.precision)
+                                                         self.precision, prior=prior)
                 by_type = explicit is None and self.normalization_type != NormalizationType.NONE
                 if by_type or self.collect_statistics:
                     st = self._coordinate_statistics(data, co.shard_id, co.glm_data)

@@ -194,6 +194,15 @@ class RandomEffectModel:
             return k.to(dev), v.to(dev)
         return torch.from_numpy(self._host[0]).to(dev), torch.from_numpy(self._host[1]).to(dev)
 
+    def variance_tensor(self, device) -> Optional[torch.Tensor]:
+        """The variances as a torch tensor on ``device`` (aligned with :meth:`tensors`), None without variances."""
+        dev = torch.device(device)
+        if self._dev is not None:
+            var = self._d()[2]
+            return None if var is None else var.to(dev)
+        var = self._host[2]
+        return None if var is None else torch.from_numpy(var).to(dev)
+
     def sum_abs_and_sq(self, need_abs: bool = True):
         """(sum |w|, sum w^2) over all coefficients (regularization term value), computed where they live.
         ``need_abs=False`` on a lazy model returns (nan, ||beta||^2) without materialising it."""

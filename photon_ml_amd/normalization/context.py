@@ -44,6 +44,17 @@ class NormalizationContext:
         if self.shifts is not None and float(self.shifts[self.intercept_id]) != 0.0:
             raise ValueError("The intercept should not be transformed (shift != 0)")
 
+    @staticmethod
+    def prior_scaling(sigma: torch.Tensor) -> "NormalizationContext":
+        """Internal: the factors-only context of a Gaussian prior (incremental training, ``optimization/problem.py``):
+        ``w - mu = sigma * v`` for EVERY coefficient, the intercept included. The constructor's "intercept factor must
+        be 1" check guards user-built contexts that name an intercept; this context names none (``intercept_id`` is
+        None: there is no shift to fold into it), so every factor is taken as given."""
+        sigma = torch.as_tensor(sigma, dtype=torch.float64)
+        if not (bool(torch.isfinite(sigma).all()) and bool((sigma > 0).all())):
+            raise ValueError("prior standard deviations must be finite and positive")
+        return NormalizationContext(sigma, None, None)
+
     @property
     def is_identity(self) -> bool:
         return self.factors is None and self.shifts is None

@@ -724,6 +724,39 @@ __global__ __launch_bounds__(256) void csr_gather_rows_kernel(const long long* _
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// Prior fold (incremental training, data/random_effect.py): a Gaussian prior N(mu_j, sigma_j^2) per packed
+// coefficient becomes plain L2 on column-scaled data with shifted offsets (w = mu + sigma v). One pass over the
+// entity-sorted CSR (nip, pos, val): m[r] = sum_k val[k] mu[pos[k]] with the ORIGINAL values (the prior model's
+// score on row r), then val[k] *= sigma[pos[k]] IN PLACE (every entry is read and written by the same lane; no second
+// copy of the values). One 16-lane row per CSR row: lanes stride the row's entries by 16 with one fp64 partial each,
+// then a fixed xor butterfly over the 16 lanes. No atomics: every launch gives the same bits. Empty rows write 0.
+#define FOLD_GROUP 16
+#define FOLD_THREADS 256
+#define FOLD_ROWS_PER_BLOCK (FOLD_THREADS / FOLD_GROUP)
+__global__ __launch_bounds__(FOLD_THREADS) void prior_fold_kernel(const long long* __restrict__ nip,
+                                                                  const long long* __restrict__ pos,
+                                                                  double* __restrict__ val, long long n_rows,
+                                                                  const double* __restrict__ mu,
+                                                                  const double* __restrict__ sigma,
+                                                                  double* __restrict__ m) {
+  const long long row = (long long)blockIdx.x * FOLD_ROWS_PER_BLOCK + (threadIdx.x / FOLD_GROUP);
+  const int g = threadIdx.x % FOLD_GROUP;
+  double s = 0.0;
+  if (row < n_rows) {
+    const long long lo = nip[row], hi = nip[row + 1];
+    for (long long p = lo + g; p < hi; p += FOLD_GROUP) {
+      const long long c = pos[p];
+      const double v = val[p];
+      s += v * mu[c];
+      val[p] = v * sigma[c];
+    }
+  }
+#pragma unroll
+  for (int o = FOLD_GROUP / 2; o > 0; o >>= 1) s += __shfl_xor(s, o, FOLD_GROUP);
+  if (g == 0 && row < n_rows) m[row] = s;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
 // K12 per-group ranking metrics (AUC:tag, PRECISION@k:tag; evaluation/segmented.py): one fp64 value per group of a
 // group-ordered row layout (seg_ptr over groups, perm = row position of every group-ordered slot, group-ordered
 // weights and positive flags). Groups are bucketed by length on the host and every bucket has its own execution:
@@ -1533,6 +1566,18 @@ int pml_csr_gather_rows(int c16, const long long* nip, const long long* pos, con
   else
     hipLaunchKernelGGL(csr_gather_rows_kernel<long long>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
                        nip, pos, val, rows, nr, optr, cbase, (long long*)ocol, oval);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// m[r] = sum_k val[k] mu[pos[k]] over row r of (nip, pos, val), then val[k] *= sigma[pos[k]] in place
+int pml_prior_fold(const long long* nip, const long long* pos, double* val, long long n_rows, const double* mu,
+                   const double* sigma, double* m, void* stream) {
+  if (n_rows <= 0) return 0;
+  const long long blocks = (n_rows + FOLD_ROWS_PER_BLOCK - 1) / FOLD_ROWS_PER_BLOCK;
+  if (blocks > 0x7fffffffLL) return -22;
+  hipLaunchKernelGGL(prior_fold_kernel, dim3((unsigned)blocks), dim3(FOLD_THREADS), 0, (hipStream_t)stream, nip, pos,
+                     val, n_rows, mu, sigma, m);
   LAUNCH_CHECK();
   return 0;
 }

@@ -799,6 +799,9 @@ def game_lib() -> Optional[ctypes.CDLL]:
         lib.pml_csr_gather_rows.restype = c_int
         lib.pml_key_hist.argtypes = [c_int, c_void_p, ctypes.c_longlong, ctypes.c_longlong, c_void_p, c_void_p]
         lib.pml_key_hist.restype = c_int
+        lib.pml_prior_fold.argtypes = [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]
+        lib.pml_prior_fold.restype = c_int
         lib.pml_tl_compact.argtypes = [c_int, c_int, ctypes.POINTER(CmpArgs), c_void_p]
         lib.pml_tl_compact.restype = c_int
         lib.pml_seg_rank_eval.argtypes = [c_int, c_int, ctypes.POINTER(SegRankArgs), c_int, c_void_p]
@@ -894,6 +897,55 @@ def csr_gather_rows(nip: torch.Tensor, pos: torch.Tensor, val: torch.Tensor, row
         optr.data_ptr(), None if cbase is None else cbase.data_ptr(), ocol.data_ptr(), oval.data_ptr(),
         stream_handle(dev)), "csr_gather_rows")
     return ocol, oval
+
+
+def check_prior_fold_inputs(nip: torch.Tensor, pos: torch.Tensor, val: torch.Tensor, mu: torch.Tensor,
+                            sigma: torch.Tensor) -> None:
+    """Host-side check of everything ``prior_fold_kernel`` indexes by (``PML_CHECK_KERNEL_INPUTS=1``; same role as
+    ``DeviceGLMData.validate``): the row pointer starts at 0, never decreases and ends at the number of entries,
+    ``0 <= pos < d_total``, ``sigma`` finite and positive, ``mu`` finite. Raises ValueError; nothing is launched."""
+    nnz, d_total = int(val.numel()), int(mu.numel())
+    if pos.numel() != nnz or sigma.numel() != d_total or nip.numel() < 1:
+        raise ValueError(f"prior_fold: {pos.numel()} columns for {nnz} values, {sigma.numel()} sigma for {d_total} mu, "
+                         f"{nip.numel()} row pointers")
+    ip = nip.cpu()
+    if int(ip[0]) != 0 or int(ip[-1]) != nnz or (ip.numel() > 1 and bool((ip[1:] < ip[:-1]).any())):
+        raise ValueError(f"prior_fold: row pointer must run from 0 to {nnz} without decreasing")
+    if nnz:
+        lo, hi = (int(v) for v in torch.aminmax(pos))
+        if lo < 0 or hi >= d_total:
+            raise ValueError(f"prior_fold: coefficient positions [{lo}, {hi}] outside [0, {d_total})")
+    if d_total and not (bool(torch.isfinite(sigma).all()) and bool((sigma > 0).all())):
+        raise ValueError("prior_fold: sigma must be finite and positive")
+    if d_total and not bool(torch.isfinite(mu).all()):
+        raise ValueError("prior_fold: mu must be finite")
+
+
+def prior_fold(nip: torch.Tensor, pos: torch.Tensor, val: torch.Tensor, mu: torch.Tensor,
+               sigma: torch.Tensor) -> torch.Tensor:
+    """Fold a per-coefficient Gaussian prior into the CSR ``(nip, pos, val)`` (int64 / int64 / fp64): returns the
+    prior margins ``m[r] = sum_k val[k] mu[pos[k]]`` of every row (original values) and scales ``val[k] *=
+    sigma[pos[k]]`` IN PLACE (no second copy of the values). ``prior_fold_kernel`` on the GPU (fp64, bitwise
+    repeatable); the same definition in torch off the GPU."""
+    n = int(nip.numel()) - 1
+    dev = val.device
+    if os.environ.get("PML_CHECK_KERNEL_INPUTS", "0") == "1":
+        check_prior_fold_inputs(nip, pos, val, mu, sigma)
+    if dev.type != "cuda":
+        rows = torch.repeat_interleave(torch.arange(n, device=dev), nip[1:] - nip[:-1], output_size=int(val.numel()))
+        m = torch.zeros(n, dtype=torch.float64, device=dev).index_add_(0, rows, val * mu[pos])
+        val.mul_(sigma[pos])
+        return m
+    for t_ in (nip, pos):
+        assert t_.dtype == torch.int64 and t_.is_cuda and t_.is_contiguous()
+    for t_ in (val, mu, sigma):
+        assert t_.dtype == torch.float64 and t_.is_cuda and t_.is_contiguous()
+    assert pos.numel() == val.numel() and mu.numel() == sigma.numel() and n >= 0
+    m = torch.empty(n, dtype=torch.float64, device=dev)
+    if n:
+        check(require_game_lib().pml_prior_fold(nip.data_ptr(), pos.data_ptr(), val.data_ptr(), n, mu.data_ptr(),
+                                                sigma.data_ptr(), m.data_ptr(), stream_handle(dev)), "prior_fold")
+    return m
 
 
 SEG_RANK_CLASSES = ("C16", "C64", "CWG", "LONG")
