@@ -297,6 +297,7 @@ class RandomEffectCoordinate(Coordinate):
         self.loss = loss_for_task(self.task)
         self.device = torch.device(device) if device is not None else default_device()
         self.has_prior = prior is not None
+        self._entity_subset, self._prior = entity_subset, prior      # the dataset's build arguments (_restore_csr)
         if self.has_prior:
             if data_config.projector_type.kind.value == "RANDOM":
                 raise ValueError(f"coordinate {coordinate_id}: a prior model cannot be combined with the RANDOM "
@@ -381,9 +382,9 @@ class RandomEffectCoordinate(Coordinate):
         self._v_sq = None
         if getattr(self, "_rs", None) is not None:
             self._rs.beta = None
-        comps = getattr(self, "_comps", None)
-        if comps is not None and comps[1] is not None:
-            comps[1].W = None
+        for comps, _ in getattr(self, "_comps_by_kind", {}).values():
+            if comps[1] is not None:
+                comps[1].W = None
         self._sub_W = None
 
     def initialize_model(self):
@@ -663,30 +664,47 @@ class RandomEffectCoordinate(Coordinate):
         return out
 
     def _components(self, l1: float, oc):
-        """Solver components of the segmented coordinate, built once per dataset: ``(rs, fused, sub)`` = the
-        row-space batch (wide entities, ``row_space.py``), the fused per-entity primal TRON batch
-        (``entity_tron.py``) and the leftover entities as a block-diagonal sub-problem for the pass path (any of
-        them None when empty). None when the fused primal TRON does not apply to this configuration or the
-        segmented CSR was already released by an earlier split."""
+        """Solver components of the segmented coordinate, built once per dataset and solver kind: ``(rs, fused,
+        sub)`` = the row-space batch (wide entities, ``row_space.py``), the fused per-entity batch (primal TRON,
+        ``entity_tron.py``, or L-BFGS / OWL-QN for an L1 weight, ``entity_lbfgs.py``; L1 has no row-space batch)
+        and the leftover entities as a block-diagonal sub-problem for the pass path (any of them None when empty).
+        None when no fused solver applies to this configuration or the segmented CSR is not available. The cache is
+        keyed by solver kind: a ``set_config`` from TRON / L2 to L-BFGS / L1 or back never reuses the other
+        solver's batch."""
+        from ..optimization.entity_lbfgs import EntityLbfgsBatch, fused_lbfgs_eligible
         from ..optimization.entity_tron import EntityTronBatch, fused_eligible
         opt = "TRON" if oc.optimizer_type == OptimizerType.TRON else "LBFGS"
         ds = self.dataset
         seg = ds.seg
-        if not fused_eligible(self.loss, opt, l1, oc.constraint_map, seg.y.device):
+        if fused_eligible(self.loss, opt, l1, oc.constraint_map, seg.y.device):
+            kind = "tron"
+        elif fused_lbfgs_eligible(self.loss, opt, l1, oc.constraint_map, seg.y.device):
+            kind = "lbfgs"
+        else:
             return None
-        cached = getattr(self, "_comps", None)
+        by_kind = self.__dict__.setdefault("_comps_by_kind", {})
+        cached = by_kind.get(kind)
         if cached is not None:
-            return cached
+            if self.__dict__.get("_comps") is not cached[0]:
+                self._comps, self._w_covered = cached
+                self._sub_W = None
+            return cached[0]
+        if getattr(ds, "_seg_csr", None) is None and by_kind:
+            # released after the other solver kind's setup: derived again from the data (a solver-kind switch is
+            # rare; keeping the CSR for it would cost 24 B per non-zero for the coordinate's whole life)
+            self._restore_csr()
         if getattr(ds, "_seg_csr", None) is None:
             return None
         with Timed(f"RE {self.coordinate_id}: solver components", log, logging.DEBUG):
-            with Timed(f"RE {self.coordinate_id}: row-space batch", log, logging.DEBUG):
-                rs = self._row_space(l1, oc)
-                rs = rs if rs is not None and rs.B else None
+            rs = None
+            if kind == "tron":
+                with Timed(f"RE {self.coordinate_id}: row-space batch", log, logging.DEBUG):
+                    rs = self._row_space(l1, oc)
+                    rs = rs if rs is not None and rs.B else None
             n_e = seg.row_ptr[1:] - seg.row_ptr[:-1]
             done = rs.mask.clone() if rs is not None else torch.zeros(seg.B, dtype=torch.bool, device=seg.y.device)
             with Timed(f"RE {self.coordinate_id}: fused primal batch", log, logging.DEBUG):
-                fused = EntityTronBatch(ds, (~done) & (n_e > 0))
+                fused = (EntityTronBatch if kind == "tron" else EntityLbfgsBatch)(ds, (~done) & (n_e > 0))
             if fused.B:
                 done |= fused.mask
             else:
@@ -701,11 +719,23 @@ class RandomEffectCoordinate(Coordinate):
             cov += (0 if fused is None else int(fused.cols.numel())) + (0 if sub is None else int(sub.cols.numel()))
             self._w_covered = cov == int(seg.col_ptr[-1])
         self._comps = (rs, fused, sub)
+        by_kind[kind] = (self._comps, self._w_covered)
         self._sub_W = None
-        log.debug("RE %s: %d row-space, %d fused primal, %d pass-path entities", self.coordinate_id,
-                  0 if rs is None else rs.B, 0 if fused is None else fused.B,
+        log.debug("RE %s: %d row-space, %d fused %s, %d pass-path entities", self.coordinate_id,
+                  0 if rs is None else rs.B, 0 if fused is None else fused.B, kind,
                   0 if sub is None else sub.entities.numel())
         return self._comps
+
+    def _restore_csr(self):
+        """The segmented per-entity CSR again after ``release_csr``: the dataset build is deterministic, so a
+        second build over the same data yields the same rows, columns and values."""
+        ds = self.dataset
+        with Timed(f"RE {self.coordinate_id}: segmented CSR rebuilt", log, logging.DEBUG):
+            again = RandomEffectDataset(self.data, self.data_config, self.device, ds.dtype,
+                                        entity_subset=self._entity_subset, layout=ds.layout, prior=self._prior)
+        csr = getattr(again, "_seg_csr", None)
+        if csr is not None and int(csr[0].numel()) == int(ds.seg.y.numel()) + 1:
+            ds._seg_csr = csr
 
     def solver_routing(self) -> dict:
         """Where this coordinate's entities are solved (after its first update): row-space / fused primal /
@@ -801,8 +831,12 @@ class RandomEffectCoordinate(Coordinate):
         fres = None
         if fused is not None:
             with Timed(f"RE {self.coordinate_id}: fused primal solve", log, logging.DEBUG):
-                fres = fused.solve(self.loss, l2, None if W0 is None else W0[fused.cols], seg.o[fused.rows],
-                                   oc.tolerance, oc.maximum_iterations)
+                W0f = None if W0 is None else W0[fused.cols]
+                if getattr(fused, "kind", "tron") == "lbfgs":
+                    fres = fused.solve(self.loss, l2, l1, W0f, seg.o[fused.rows], oc.tolerance,
+                                       oc.maximum_iterations)
+                else:
+                    fres = fused.solve(self.loss, l2, W0f, seg.o[fused.rows], oc.tolerance, oc.maximum_iterations)
                 _sync(fres.W)
             iters.index_copy_(0, fused.ents, fres.iters)
             reasons.index_copy_(0, fused.ents, fres.reason)
@@ -818,12 +852,12 @@ class RandomEffectCoordinate(Coordinate):
             with Timed(f"RE {self.coordinate_id}: primal block-diagonal solve", log, logging.DEBUG):
                 if sub_async:
                     with torch.cuda.stream(sub_stream):
-                        res, z_sub = self._solve_sub(sub, sub_in, l2, oc)
+                        res, z_sub = self._solve_sub(sub, sub_in, l2, oc, l1)
                     main.wait_stream(sub_stream)
                     for t in (res.W, res.iters, res.reason, z_sub):
                         t.record_stream(main)
                 else:
-                    res, z_sub = self._solve_sub(sub, self._sub_inputs(sub, seg, W0), l2, oc)
+                    res, z_sub = self._solve_sub(sub, self._sub_inputs(sub, seg, W0), l2, oc, l1)
                 _sync(res.W)
             self._sub_W = res.W
             iters.index_copy_(0, sub.entities, res.iters)
@@ -892,13 +926,17 @@ class RandomEffectCoordinate(Coordinate):
         sub.seg._dzz_key = None
         return W0s
 
-    def _solve_sub(self, sub, W0s, l2: float, oc):
-        """Block-diagonal TRON over the pass-path subset (on the current stream); (result, its margins)."""
+    def _solve_sub(self, sub, W0s, l2: float, oc, l1: float = 0.0):
+        """Block-diagonal TRON (L-BFGS / OWL-QN for an L-BFGS configuration) over the pass-path subset (on the
+        current stream); (result, its margins)."""
         from ..optimization.batched import batched_tron
         o = sub.seg.o
         if o.is_cuda:
             o.record_stream(torch.cuda.current_stream(o.device))     # formed on the main stream
-        res = batched_tron(sub.seg, self.loss, l2, W0s, oc.tolerance, oc.maximum_iterations)
+        if oc.optimizer_type == OptimizerType.TRON:
+            res = batched_tron(sub.seg, self.loss, l2, W0s, oc.tolerance, oc.maximum_iterations)
+        else:
+            res = batched_lbfgs(sub.seg, self.loss, l2, W0s, oc.tolerance, oc.maximum_iterations, l1=l1)
         return res, sub.seg.glm.matvec(res.W)
 
     def _active_mask(self, device) -> torch.Tensor:

@@ -44,7 +44,7 @@ __attribute__((used)) static const char pml_build_stamp[] = "PML_BUILD_ID=" PML_
 #define RE_NW 4                 // waves per workgroup (one entity)
 #define RE_THREADS (RE_NW * 64)
 
-enum { LOSS_LOGISTIC = 0, LOSS_POISSON = 1, LOSS_SQUARED = 2 };
+enum { LOSS_LOGISTIC = 0, LOSS_POISSON = 1, LOSS_SQUARED = 2, LOSS_HINGE = 3 };
 
 template <int LOSS>
 __device__ __forceinline__ void loss_t(double z, double y, double& l, double& dl, double& d2) {
@@ -63,6 +63,13 @@ __device__ __forceinline__ void loss_t(double z, double y, double& l, double& dl
   } else if constexpr (LOSS == LOSS_POISSON) {
     const double e = exp(z);
     l = e - y * z; dl = e - y; d2 = e;
+  } else if constexpr (LOSS == LOSS_HINGE) {
+    // Rennie & Srebro smoothed hinge (function/losses.py, pointwise_loss in glm_kernels.hip): once differentiable
+    const double yy = y < 0.5 ? -1.0 : 1.0;
+    const double t = yy * z;
+    l = t <= 0.0 ? 0.5 - t : (t < 1.0 ? 0.5 * (1.0 - t) * (1.0 - t) : 0.0);
+    dl = (t < 0.0 ? -1.0 : (t < 1.0 ? t - 1.0 : 0.0)) * yy;
+    d2 = 0.0;
   } else {
     const double d = z - y;
     l = 0.5 * d * d; dl = d; d2 = 1.0;
@@ -647,6 +654,261 @@ __global__ __launch_bounds__(RE_THREADS) void re_tron_csr_kernel(ReTronArgs a) {
   if (tid == 0) {
     a.f[e] = f; a.iters[e] = it; a.reason[e] = reason;
     if (a.npass != nullptr) a.npass[e] = npass;
+  }
+}
+
+// ------------------------------------------------------------------------------------------------------------
+// Fused per-entity L-BFGS / OWL-QN (L1 and elastic-net random effects): a transcription of batched_lbfgs
+// (optimization/batched.py) for ONE entity per workgroup -- two-loop recursion over a ring of m (S, Y) pairs,
+// OWL-QN pseudo-gradient / direction alignment / orthant projection when OWL, backtracking Armijo line search,
+// Photon's convergence rules. Every function evaluation is one row_pass<1> over the entity's CSR rows; w, the smooth
+// gradient at w, the two-loop vector (then the direction) and the trial point live in LDS. The (S, Y) history is
+// too large for LDS (2 m dmax doubles) and lives in a global workspace PER RESIDENT WORKGROUP: the grid is
+// persistent and a workgroup takes its next entity from a ticket counter (largest entities first). A thread
+// reads and writes only its own coefficients j = tid + 256 q of the history, so the workspace needs no fences.
+// Floating-point contraction is off in the kernel body: products and sums round as the torch ops of
+// batched_lbfgs do (W + t d, q - a Y, f + 1e-4 t g.d are a multiply and an add there), which keeps the two
+// within summation-order rounding of each other.
+#define RE_LB_MMAX 10                // history pairs at most (the two-loop coefficients stay in registers)
+
+struct ReLbfgsArgs {
+  ReTronArgs a;              // data, outputs, l2, tol, max_iter, dmax (max_fail / max_cg / gsc / xf2 unused)
+  double l1;
+  int m, max_ls;             // history pairs (<= RE_LB_MMAX), line-search trials
+  double* hist;              // [grid][2][m][dmax] S then Y of each resident workgroup
+  int* ticket;               // dequeue counter (zero before the launch)
+};
+
+template <int LOSS, bool OWL>
+__global__ __launch_bounds__(RE_THREADS) void re_lbfgs_csr_kernel(ReLbfgsArgs p) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  __shared__ int sTicket;
+  const ReTronArgs& a = p.a;
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  const int dm = a.dmax, m = p.m;
+  const double l1 = p.l1;
+  double* sW = smem;
+  double* sGs = sW + dm;    // smooth gradient at W (the pseudo-gradient is formed from sW, sGs, l1 on the fly)
+  double* sQ = sGs + dm;    // two-loop vector, then the search direction
+  double* sT = sQ + dm;     // trial point
+  double* acc = sT + dm;    // RE_NW accumulators; acc[0 .. d) = smooth gradient of the last evaluation
+  double* red = acc + RE_NW * dm;
+  double* rho = red + 2 * RE_NW * 8;
+  double* myacc = acc + w * dm;
+  double* hS = p.hist + (size_t)blockIdx.x * 2 * m * dm;
+  double* hY = hS + (size_t)m * dm;
+  double* D[2] = {a.scr, a.scr + a.n_rows};
+  double* Z[2] = {a.scr + 2 * a.n_rows, a.scr + 3 * a.n_rows};
+
+  // OWL-QN pseudo-gradient component (the smooth gradient itself without L1)
+  auto pgrad = [&](double wj, double gj) -> double {
+    if (!OWL) return gj;
+    if (wj != 0.0) return gj + (wj > 0.0 ? l1 : -l1);
+    const double dminus = gj - l1, dplus = gj + l1;
+    return dminus > 0.0 ? dminus : (dplus < 0.0 ? dplus : 0.0);
+  };
+
+  for (;;) {
+    __syncthreads();
+    if (tid == 0) sTicket = atomicAdd(p.ticket, 1);
+    __syncthreads();
+    const int tk = sTicket;
+    if (tk >= a.n_launch) break;
+    const int e = a.order[tk];
+    const long long r0 = a.row_ptr[e], r1 = a.row_ptr[e + 1];
+    const long long c0 = a.col_ptr[e];
+    const int d = (int)(a.col_ptr[e + 1] - c0);
+    int cur = 0, parity = 0, npass = 0;
+    double* Wg = a.W + c0;
+
+    auto zero_own = [&]() {
+      for (int j = lane; j < d; j += 64) myacc[j] = 0.0;
+    };
+    // smooth value + gradient at vec (MODE 1: writes D / Z buffer ``nb``); the gradient lands in acc[0 .. d) after
+    // the fixed-order wave combine; gg = ||g||^2, an = ||vec||_1
+    auto value_grad = [&](const double* vec, int nb, bool at_zero, double& gg, double& an) -> double {
+      ++npass;
+      __syncthreads();
+      zero_own();
+      double fp = 0.0;
+      if (at_zero) row_pass<2, LOSS>(a, r0, r1, vec, myacc, nullptr, nullptr, nullptr, fp);
+      else row_pass<1, LOSS>(a, r0, r1, vec, myacc, nullptr, D[nb], Z[nb], fp);
+      __syncthreads();
+      double s4[4] = {fp, 0.0, 0.0, 0.0};
+      for (int j = tid; j < d; j += RE_THREADS) {
+        double g = acc[j];
+#pragma unroll
+        for (int q = 1; q < RE_NW; ++q) g += acc[q * dm + j];
+        const double v = vec[j];
+        g += a.l2 * v;
+        acc[j] = g;
+        s4[1] += v * v;
+        s4[2] += g * g;
+        s4[3] += fabs(v);
+      }
+      block_sums<4>(s4, red, parity);
+      gg = s4[2];
+      an = s4[3];
+      return s4[0] + 0.5 * a.l2 * s4[1];
+    };
+
+    for (int j = tid; j < d; j += RE_THREADS) sW[j] = Wg[j];
+    double gs2, an;
+    double f = value_grad(sW, cur, false, gs2, an);
+    double s2[2] = {0.0, 0.0};
+    for (int j = tid; j < d; j += RE_THREADS) {
+      const double wj = sW[j], gj = acc[j];
+      sGs[j] = gj;
+      s2[0] += wj != 0.0 ? 1.0 : 0.0;
+      const double pj = pgrad(wj, gj);
+      s2[1] += pj * pj;
+    }
+    block_sums<2>(s2, red, parity);
+    double pg2 = s2[1];                        // ||pseudo-gradient||^2 at W
+    double f0z = f, g0n = sqrt(gs2);           // tolerances from the SMOOTH state at zero (as _Convergence)
+    if (s2[0] != 0.0) {
+      for (int j = tid; j < d; j += RE_THREADS) sT[j] = 0.0;
+      double g0, a0;
+      f0z = value_grad(sT, 0, true, g0, a0);
+      g0n = sqrt(g0);
+    }
+    const double loss_tol = f0z * a.tol, grad_tol = g0n * a.tol;
+    if (OWL) f = f + l1 * an;
+    int it = 0, reason = 0, nh = 0, head = m - 1;
+    bool active = true;
+    if (!(pg2 > 0.0)) { reason = 4; active = false; }
+
+    for (int guard = 0; active && guard < a.max_iter + 2; ++guard) {
+      // ---- two-loop recursion on the pseudo-gradient; recency k lives in ring slot (head - k) mod m
+      for (int j = tid; j < d; j += RE_THREADS) sQ[j] = pgrad(sW[j], sGs[j]);
+      double alpha[RE_LB_MMAX] = {};
+      double yy = 0.0;
+#pragma unroll
+      for (int k = 0; k < RE_LB_MMAX; ++k) {
+        if (k < nh) {
+          const int slot = (head - k + m) % m;
+          const double* S = hS + (size_t)slot * dm;
+          const double* Y = hY + (size_t)slot * dm;
+          double s[2] = {0.0, 0.0};
+          for (int j = tid; j < d; j += RE_THREADS) {
+            s[0] += S[j] * sQ[j];
+            if (k == 0) s[1] += Y[j] * Y[j];
+          }
+          block_sums<2>(s, red, parity);
+          if (k == 0) yy = s[1];
+          const double ak = rho[slot] * s[0];
+          alpha[k] = ak;
+          for (int j = tid; j < d; j += RE_THREADS) sQ[j] = sQ[j] - ak * Y[j];
+        }
+      }
+      if (nh > 0) {
+        const double den = rho[head] * yy;
+        const double scale = 1.0 / (den > 1e-300 ? den : 1e-300);
+        for (int j = tid; j < d; j += RE_THREADS) sQ[j] = sQ[j] * scale;
+      }
+#pragma unroll
+      for (int k = RE_LB_MMAX - 1; k >= 0; --k) {
+        if (k < nh) {
+          const int slot = (head - k + m) % m;
+          const double* S = hS + (size_t)slot * dm;
+          const double* Y = hY + (size_t)slot * dm;
+          double s[1] = {0.0};
+          for (int j = tid; j < d; j += RE_THREADS) s[0] += Y[j] * sQ[j];
+          block_sums<1>(s, red, parity);
+          const double c = alpha[k] - rho[slot] * s[0];
+          for (int j = tid; j < d; j += RE_THREADS) sQ[j] = sQ[j] + c * S[j];
+        }
+      }
+      // ---- direction -q (OWL: components that do not descend along the pseudo-gradient are dropped)
+      double s3[3] = {0.0, 0.0, 0.0};
+      for (int j = tid; j < d; j += RE_THREADS) {
+        const double pj = pgrad(sW[j], sGs[j]);
+        double dj = -sQ[j];
+        if (OWL) dj = dj * pj < 0.0 ? dj : 0.0;
+        sQ[j] = dj;
+        s3[0] += pj * dj;
+        s3[1] += dj * dj;
+        s3[2] += pj * (-pj);
+      }
+      block_sums<3>(s3, red, parity);
+      double gd = s3[0], dd = s3[1];
+      if (gd >= 0.0) {             // not a descent direction: steepest descent, history dropped
+        for (int j = tid; j < d; j += RE_THREADS) sQ[j] = -pgrad(sW[j], sGs[j]);
+        nh = 0;
+        gd = s3[2];
+        dd = -s3[2];
+      }
+      // ---- backtracking Armijo line search over orthant-projected trial points
+      const double dn = sqrt(dd > 0.0 ? dd : 0.0);
+      double t = it == 0 ? 1.0 / (dn > 1e-300 ? dn : 1e-300) : 1.0;
+      const double shrink = it == 0 ? (OWL ? 0.1 : 0.5) : 0.5;
+      bool found = false;
+      double ft = f, gt2 = 0.0;
+      for (int ls = 0; ls < p.max_ls && !found; ++ls) {
+        for (int j = tid; j < d; j += RE_THREADS) {
+          const double wj = sW[j];
+          double x = wj + t * sQ[j];
+          if (OWL) {
+            const double o = wj != 0.0 ? wj : -pgrad(wj, sGs[j]);     // the orthant's sign
+            x = ((x > 0.0 && o > 0.0) || (x < 0.0 && o < 0.0)) ? x : 0.0;
+          }
+          sT[j] = x;
+        }
+        double at;
+        ft = value_grad(sT, cur ^ 1, false, gt2, at);
+        if (OWL) ft = ft + l1 * at;
+        found = isfinite(ft) && ft <= f + 1e-4 * t * gd;
+        if (!found) t = t * shrink;
+      }
+      // ---- accepted point: history pair (s, y of the SMOOTH gradients), new state
+      const double f_prev = f;
+      if (found) {
+        double u2[2] = {0.0, 0.0};
+        for (int j = tid; j < d; j += RE_THREADS) {
+          const double x = sT[j], gj = acc[j];
+          u2[0] += (x - sW[j]) * (gj - sGs[j]);
+          const double pj = pgrad(x, gj);
+          u2[1] += pj * pj;
+        }
+        block_sums<2>(u2, red, parity);
+        const double sy = u2[0];
+        pg2 = u2[1];
+        const bool upd = sy > 1e-300;
+        if (upd) {
+          head = (head + 1) % m;
+          nh = nh < m ? nh + 1 : m;
+          if (tid == 0) rho[head] = 1.0 / sy;
+        }
+        double* S = hS + (size_t)head * dm;
+        double* Y = hY + (size_t)head * dm;
+        for (int j = tid; j < d; j += RE_THREADS) {
+          const double x = sT[j], gj = acc[j];
+          if (upd) { S[j] = x - sW[j]; Y[j] = gj - sGs[j]; }
+          sW[j] = x;
+          sGs[j] = gj;
+        }
+        f = ft;
+        cur ^= 1;
+        ++it;
+      }
+      int rc = 0;
+      if (found && sqrt(pg2 > 0.0 ? pg2 : 0.0) <= grad_tol) rc = 4;
+      if (found && fabs(f - f_prev) <= loss_tol) rc = 3;
+      if (!found) rc = 2;
+      if (it >= a.max_iter) rc = 1;
+      if (rc > 0) { reason = rc; active = false; }
+    }
+    __syncthreads();
+    for (int j = tid; j < d; j += RE_THREADS) Wg[j] = sW[j];
+    if (a.zout != nullptr) {
+      const double* zc = Z[cur];
+      for (long long i = r0 + tid; i < r1; i += RE_THREADS) a.zout[i] = zc[i];
+    }
+    if (tid == 0) {
+      a.f[e] = f; a.iters[e] = it; a.reason[e] = reason;
+      if (a.npass != nullptr) a.npass[e] = npass;
+    }
   }
 }
 
@@ -1956,6 +2218,58 @@ int pml_re_tron_csr(const int* order, int n_launch, const long long* row_ptr, co
   if (loss == LOSS_LOGISTIC) hipLaunchKernelGGL(re_tron_csr_kernel<0>, dim3(n_launch), dim3(RE_THREADS), smem, st, a);
   else if (loss == LOSS_POISSON) hipLaunchKernelGGL(re_tron_csr_kernel<1>, dim3(n_launch), dim3(RE_THREADS), smem, st, a);
   else hipLaunchKernelGGL(re_tron_csr_kernel<2>, dim3(n_launch), dim3(RE_THREADS), smem, st, a);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// Fused per-entity L-BFGS / OWL-QN (re_lbfgs_csr_kernel): LDS of one workgroup for entities of at most ``dmax``
+// coefficients (w, smooth gradient, direction, trial point, RE_NW accumulators, reduction slots, rho[m]).
+size_t pml_re_lbfgs_smem(int dmax) {
+  return ((size_t)(4 + RE_NW) * dmax + 2 * RE_NW * 8 + RE_LB_MMAX) * sizeof(double);
+}
+
+// Workgroups of the L-BFGS kernel resident on the device at once for ``dmax`` (occupancy API x CUs; 0 on error):
+// the persistent grid, and the number of history workspaces (2 m dmax doubles each) a launch needs.
+int pml_re_lbfgs_grid(int dmax) {
+  int dev = 0, cus = 0, per = 0;
+  if (dmax <= 0 || pml_re_lbfgs_smem(dmax) > 160 * 1024) return 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, (const void*)re_lbfgs_csr_kernel<0, true>, RE_THREADS,
+                                                   pml_re_lbfgs_smem(dmax)) != hipSuccess) return 0;
+  return cus * per;
+}
+
+// Persistent launch of min(n_launch, grid) workgroups over the entities ``order`` (largest first). The data and
+// output arguments are pml_re_tron_csr's; ``l1`` > 0 selects OWL-QN; ``hist``: grid x 2 x m x dmax doubles;
+// ``ticket`` (1 int) is zeroed here on the stream.
+int pml_re_lbfgs_csr(const int* order, int n_launch, const long long* row_ptr, const long long* col_ptr,
+                     const long long* nip, const uint16_t* lcol, const double* val, const double* y,
+                     const double* off, const double* wt, double* scr, long long n_rows, double* W, double* f,
+                     int* iters, int* reason, double* zout, int* npass, int loss, double l2, double tol,
+                     int max_iter, int dmax, double l1, int m, int max_ls, double* hist, int* ticket, int grid,
+                     hipStream_t st) {
+  if (n_launch <= 0) return 0;
+  if (dmax <= 0 || loss < 0 || loss > 3 || m < 1 || m > RE_LB_MMAX || max_ls < 1 || max_iter < 0 || grid <= 0 ||
+      !(l1 >= 0.0) || hist == nullptr || ticket == nullptr)
+    return -22;
+  const size_t smem = pml_re_lbfgs_smem(dmax);
+  if (smem > 160 * 1024) return -22;
+  if (hipMemsetAsync(ticket, 0, sizeof(int), st) != hipSuccess) return -5;
+  ReLbfgsArgs p{{order, n_launch, row_ptr, col_ptr, nip, lcol, val, y, off, wt, scr, n_rows, W, f, iters, reason,
+                 zout, npass, loss, l2, tol, max_iter, 0, 0, dmax},
+                l1, m, max_ls, hist, ticket};
+  const dim3 g(n_launch < grid ? n_launch : grid), b(RE_THREADS);
+#define RL_LAUNCH(L)                                                                       \
+  do {                                                                                     \
+    if (l1 > 0.0) hipLaunchKernelGGL((re_lbfgs_csr_kernel<L, true>), g, b, smem, st, p);   \
+    else hipLaunchKernelGGL((re_lbfgs_csr_kernel<L, false>), g, b, smem, st, p);           \
+  } while (0)
+  if (loss == LOSS_LOGISTIC) RL_LAUNCH(0);
+  else if (loss == LOSS_POISSON) RL_LAUNCH(1);
+  else if (loss == LOSS_SQUARED) RL_LAUNCH(2);
+  else RL_LAUNCH(3);
+#undef RL_LAUNCH
   LAUNCH_CHECK();
   return 0;
 }

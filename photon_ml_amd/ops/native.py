@@ -1478,6 +1478,14 @@ def re_lib() -> Optional[ctypes.CDLL]:
         lib.pml_re_res_grid.restype = c_int
         lib.pml_re_res_ws_doubles.argtypes = [c_int]
         lib.pml_re_res_ws_doubles.restype = ctypes.c_size_t
+        lib.pml_re_lbfgs_csr.argtypes = ([c_void_p, c_int] + [c_void_p] * 9 + [ctypes.c_longlong] + [c_void_p] * 6
+                                         + [c_int, c_double, c_double, c_int, c_int, c_double, c_int, c_int,
+                                            c_void_p, c_void_p, c_int, c_void_p])
+        lib.pml_re_lbfgs_csr.restype = c_int
+        lib.pml_re_lbfgs_smem.argtypes = [c_int]
+        lib.pml_re_lbfgs_smem.restype = ctypes.c_size_t
+        lib.pml_re_lbfgs_grid.argtypes = [c_int]
+        lib.pml_re_lbfgs_grid.restype = c_int
         lib._pml_typed = True
     return lib
 
@@ -1559,6 +1567,59 @@ def re_tron_csr(order, row_ptr, col_ptr, nip, lcol, val, y, off, wt, scr, W, f, 
         return
     fn = lib.pml_re_tron_hess if hessian else lib.pml_re_tron_csr
     check(fn(*args, stream_handle(W.device)), "re_tron_csr")
+
+
+RE_LBFGS_M = 10          # history pairs of the fused L-BFGS / OWL-QN kernel (its compile-time maximum)
+
+
+def re_lbfgs_grid(dmax: int) -> int:
+    """Workgroups of ``re_lbfgs_csr_kernel`` resident on the current device for entities of at most ``dmax``
+    coefficients: the persistent grid of a launch, one history workspace each."""
+    grid = int(require_re_lib().pml_re_lbfgs_grid(int(dmax)))
+    if grid <= 0:
+        raise RuntimeError(f"re_lbfgs_csr_kernel: no resident workgroup for dmax={dmax}")
+    return grid
+
+
+def re_lbfgs_csr(order, row_ptr, col_ptr, nip, lcol, val, y, off, wt, scr, W, f, iters, reason, zout, loss_id: int,
+                 l2: float, l1: float, tol: float, max_iter: int, dmax: int, hist: torch.Tensor,
+                 ticket: torch.Tensor, grid: int, m: int = RE_LBFGS_M, max_ls: int = 30,
+                 npass: Optional[torch.Tensor] = None) -> None:
+    """Fused per-entity L-BFGS (``l1 == 0``) / OWL-QN (``l1 > 0``) over the entities ``order`` of a block-diagonal
+    CSR (``re_lbfgs_csr_kernel``): ONE persistent launch of ``min(len(order), grid)`` workgroups, each solving one
+    entity at a time with the semantics of ``optimization.batched.batched_lbfgs``. Data and outputs as
+    :func:`re_tron_csr` (``f`` is the objective including the L1 term); losses 0..3 (smoothed hinge included).
+    ``hist``: fp64 workspace of at least ``grid x 2 x m x dmax`` (the (S, Y) history of each resident workgroup);
+    ``ticket``: int32[1], zeroed by the launch. Device only; in place, nothing returned."""
+    lib = require_re_lib()
+    n_rows = y.numel()
+    B = int(order.numel())
+    for t in (order, row_ptr, col_ptr, nip, lcol, val, y, off, wt, scr, W, f, iters, reason, zout, hist, ticket):
+        assert t.is_cuda and t.is_contiguous() and t.device == W.device
+    assert order.dtype == torch.int32 and row_ptr.dtype == col_ptr.dtype == nip.dtype == torch.int64
+    assert lcol.dtype == torch.int16 and nip.numel() == n_rows + 1 and lcol.numel() == val.numel()
+    assert all(t.dtype == torch.float64 for t in (val, y, off, wt, scr, W, f, zout, hist))
+    assert off.numel() == n_rows and wt.numel() == n_rows and zout.numel() == n_rows and scr.numel() >= 4 * n_rows
+    assert iters.dtype == reason.dtype == ticket.dtype == torch.int32 and ticket.numel() >= 1
+    n_ent = row_ptr.numel() - 1
+    assert col_ptr.numel() == n_ent + 1 and f.numel() == n_ent and iters.numel() == n_ent and reason.numel() == n_ent
+    assert dmax > 0 and dmax % 64 == 0 and 1 <= m <= RE_LBFGS_M and max_ls >= 1 and grid >= 1 and l1 >= 0
+    assert hist.numel() >= min(B, grid) * 2 * m * dmax, "history workspace too small for the persistent grid"
+    if npass is not None:
+        assert npass.is_cuda and npass.dtype == torch.int32 and npass.numel() == n_ent
+    if os.environ.get("PML_CHECK_KERNEL_INPUTS", "0") == "1" and B:
+        assert int(order.min()) >= 0 and int(order.max()) < n_ent, "re_lbfgs order out of range"
+        oe = order.to(torch.int64)
+        assert int((col_ptr[oe + 1] - col_ptr[oe]).max()) <= dmax, "entity wider than the launch's LDS class"
+        assert W.numel() == int(col_ptr[-1]), "packed coefficients / column ranges inconsistent"
+        assert int(row_ptr[-1]) == n_rows and int(nip[-1]) <= val.numel(), "row / non-zero ranges inconsistent"
+    check(lib.pml_re_lbfgs_csr(order.data_ptr(), B, row_ptr.data_ptr(), col_ptr.data_ptr(), nip.data_ptr(),
+                               lcol.data_ptr(), val.data_ptr(), y.data_ptr(), off.data_ptr(), wt.data_ptr(),
+                               scr.data_ptr(), n_rows, W.data_ptr(), f.data_ptr(), iters.data_ptr(),
+                               reason.data_ptr(), zout.data_ptr(), None if npass is None else npass.data_ptr(),
+                               int(loss_id), float(l2), float(tol), int(max_iter), int(dmax), float(l1), int(m),
+                               int(max_ls), hist.data_ptr(), ticket.data_ptr(), int(grid),
+                               stream_handle(W.device)), "re_lbfgs_csr")
 
 
 def re_res_params():

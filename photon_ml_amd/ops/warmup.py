@@ -60,6 +60,15 @@ def runtime_warmup(device, force: bool = False) -> float:
     L = torch.eye(65, dtype=torch.float64, device=dev).unsqueeze(0).contiguous()
     batched_trsv(L, torch.ones(1, 65, dtype=torch.float64, device=dev))  # libpml_re (n > 64)
     batched_gemv(L[:, :8, :8].contiguous(), torch.ones(1, 8, dtype=torch.float64, device=dev))
+    # fused per-entity OWL-QN (persistent grid: occupancy query + one launch): one entity of one row x one coefficient
+    from .native import re_lbfgs_csr, re_lbfgs_grid
+    p01 = torch.tensor([0, 1], dtype=torch.int64, device=dev)
+    one = torch.ones(1, dtype=torch.float64, device=dev)
+    i32 = lambda: torch.zeros(1, dtype=torch.int32, device=dev)
+    re_lbfgs_csr(i32(), p01, p01, p01, torch.zeros(1, dtype=torch.int16, device=dev), one, one, torch.zeros_like(one),
+                 one, torch.empty(4, dtype=torch.float64, device=dev), torch.zeros_like(one), torch.empty_like(one),
+                 i32(), i32(), torch.empty_like(one), 0, 0.0, 0.1, 1e-3, 2, 256,
+                 torch.empty(2 * 10 * 256, dtype=torch.float64, device=dev), i32(), min(re_lbfgs_grid(256), 1))
     torch.cuda.Stream(dev, priority=-1)                                  # first prioritised stream
     torch.cuda.Stream(dev, priority=0)
     torch.cuda.synchronize(dev)
