@@ -137,7 +137,7 @@ def generate_device_shard(n_rows: int, n_features: int, nnz_per_row: int, device
                           task=TaskType.LOGISTIC_REGRESSION, rank: int = 0, progress=None, layout: str = "auto"):
     """Generate a :class:`DeviceGLMData` directly in device memory (see module docstring)."""
     from ..ops.device import DeviceGLMData, SegChunk, VAL_DTYPE, resolve_layout
-    from ..ops.tiled import TLFwdChunk, TLTChunk
+    from ..ops.tiled import TLFwdChunk, TLTChunk, shard_tall
 
     dev = torch.device(device)
     prec = {"bf16": 0, "f32": 1, "f64": 2}[precision]
@@ -198,7 +198,7 @@ def generate_device_shard(n_rows: int, n_features: int, nnz_per_row: int, device
             rp = torch.arange(0, (m + 1) * k, k, dtype=torch.int64, device=dev)
             col = idx.to(torch.int64)
             del idx
-            csr.append(TLFwdChunk(rp, col, val, n_features))
+            csr.append(TLFwdChunk(rp, col, val, n_features, tall=shard_tall(n_features, min(chunk_rows, n_rows))))
             csc.append(TLTChunk(rp, col, val, n_features, chunk_rows, cbits=cbits, item_entries=item_entries))
             raw[ci] = None
             del col, val, rp

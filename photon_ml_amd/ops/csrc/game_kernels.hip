@@ -203,7 +203,8 @@ __global__ __launch_bounds__(256) void downsample_kernel(const T* __restrict__ y
 // turns the counts into per-unit round-aligned output starts (device cumsums) and pass 1 writes. Inside a round,
 // logical entry t = 64 k + lane is placed with a ballot + popcount per k, so the copy is deterministic.
 // key_is_row = 1 (transpose copy): an entry's chunk row is its key (pack >> sbits); 0 (forward copy): the unit's
-// first row plus its slot (pack & smask).
+// first row plus its slot (pack & smask). A TALL forward unit (4 sub-blocks of 2^sbits rows, ops/tiled.py) has
+// 2^wbits slots: its narrow packs hold the row inside their sub-block and are rewritten as wide packs of the unit.
 // ------------------------------------------------------------------------------------------------------------
 #define CMP_SEG 8
 struct CmpArgs {
@@ -222,6 +223,9 @@ struct CmpArgs {
   const long long* unit_lo;     // pass 1: physical output start of every unit (round-aligned)
   uint32_t* opack;              // pass 1 outputs
   void* oval;
+  int ustride;                  // ints per unit of ``units``: 6, or 10 = tall forward units (ops/tiled.py): columns 6, 7, 8
+                                // hold the first narrow round of sub-blocks 1, 2, 3
+  int wbits;                    // slot bits of the wide packs (= sbits, tall units: 12); sbits: the narrow packs'
 };
 
 template <typename VT, int PASS>
@@ -231,12 +235,13 @@ __global__ __launch_bounds__(256) void tl_compact_kernel(CmpArgs a) {
   if (s >= a.nseg) return;                                   // wave-uniform
   const int* sg = a.seg + 3 * (long long)s;
   const int u = sg[0], r_lo = sg[1], r_hi = sg[2];
-  const int* ut = a.units + 6 * (long long)u;
+  const int* ut = a.units + a.ustride * (long long)u;
   const long long e_lo = ut[a.col_e];
   const int nw = ut[a.col_e + 1] - ut[a.col_e];
   const int n_lo = ut[4], nn = ut[5] - ut[4];
   const uint32_t row0 = a.row_col >= 0 ? (uint32_t)ut[a.row_col] : 0u;
-  const uint32_t smask = (1u << a.sbits) - 1u;
+  const uint32_t smask = (1u << a.sbits) - 1u, wmask = (1u << a.wbits) - 1u;
+  const bool tall = a.ustride > 6;
   const VT* val = (const VT*)a.val;
   const VT* nval = (const VT*)a.nval;
   long long ob = PASS ? a.seg_first[s] : 0;
@@ -250,12 +255,14 @@ __global__ __launch_bounds__(256) void tl_compact_kernel(CmpArgs a) {
     if (r < nn) {
       const long long q = (long long)n_lo + r;
       const int base = a.nbase[q];
+      // tall unit: the round's sub-block (its 1024 rows' offset in the unit) from the sub-blocks' first rounds
+      const uint32_t sub = tall ? (uint32_t)((q >= ut[6]) + (q >= ut[7]) + (q >= ut[8])) << a.sbits : 0u;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         // fused records (nval null, 2-byte values): lane's 4 packs then its 4 values in one 16-B record
         const long long pe = nval ? q * 256 + 4 * lane + k : q * 512 + 8 * lane + k;
         const uint32_t p16 = a.npack[pe];
-        p[k] = ((uint32_t)(base + (int)(p16 >> a.sbits)) << a.sbits) | (p16 & smask);
+        p[k] = ((uint32_t)(base + (int)(p16 >> a.sbits)) << a.wbits) | sub | (p16 & smask);
         v[k] = nval ? nval[pe] : ((const VT*)a.npack)[pe + 4];
         ok[k] = true;
       }
@@ -271,7 +278,7 @@ __global__ __launch_bounds__(256) void tl_compact_kernel(CmpArgs a) {
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const uint32_t row = a.key_is_row ? (p[k] >> a.sbits) : row0 + (p[k] & smask);
+      const uint32_t row = a.key_is_row ? (p[k] >> a.wbits) : row0 + (p[k] & wmask);
       const bool kp = ok[k] && a.keep[row];
       const unsigned long long m = __ballot(kp);
       if (PASS) {

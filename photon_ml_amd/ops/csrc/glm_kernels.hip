@@ -615,10 +615,15 @@ __global__ __launch_bounds__(NTHREADS) void reduce_stats_l1_kernel(const double*
 //   forward  : ROW BLOCKS of <= 2^rbits rows; inside a block entries are sorted by (column, row) and packed as
 //              (col << rbits) | local_row. Gathers x[col] walk the coefficient vector in order (hot columns, which
 //              are relabelled to the lowest indices, collapse onto one or two lines per instruction).
+//              TALL UNITS (bf16 / fp32 shards over >= 2^16 columns; tl_fwd_tall_block): 4096 rows = 4 sub-blocks of
+//              1024 rows. Narrow rounds stay per sub-block (10 slot bits); the sub-blocks' wide entries are ONE
+//              section per unit sorted by (column, row in unit) and packed (col << 12) | row12, so a tail gather
+//              reads the columns of four times as many rows and touches fewer distinct lines.
 //   transpose: COLUMN TILES of 2^cbits columns; inside a tile entries are sorted by (row, column) and packed as
 //              (local_row << cbits) | (col & (2^cbits-1)). Gathers x[row] walk the per-row vector in order.
 // Determinism: each wave owns a private LDS accumulator row and walks its entries in a fixed order, and the 4
-// wave rows are summed in a fixed order; items of a column tile that is split across work-groups write fp64
+// wave rows are summed in a fixed order (tall forward units: ONE row per work-group whose slots are added to by one
+// wave at a time -- disjoint slot ranges per wave, then a single wave after a barrier); items of a column tile that is split across work-groups write fp64
 // partial rows that a combine kernel adds IN ORDER. One assumption is MEASURED, not guaranteed by the ISA: when
 // several lanes of ONE ds_add_f64 instruction hit the same LDS address, the LDS applies them in a fixed (lane)
 // order. Every cross-instruction order is fixed by the program. Run-to-run bitwise equality is tested on each GPU
@@ -930,7 +935,8 @@ __device__ __forceinline__ void tl_stream_ring(const uint32_t* __restrict__ pack
   typedef typename TLValT<VT>::T LT;
   typedef typename TLVals<VT>::Raw Raw;
   const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  // NW == 1 (tall forward units): the calling wave, whichever it is, walks the whole window
+  const int w = NW == 1 ? 0 : __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const uint32_t smask = (1u << sbits) - 1u;
   const int nr = (e_hi - e_lo + TL_ROUND - 1) / TL_ROUND;
   const int r0 = (nr * w) / NW, r1 = (nr * (w + 1)) / NW;
@@ -1050,7 +1056,7 @@ __device__ __forceinline__ void tl_stream_narrow(const uint16_t* __restrict__ np
   typedef typename TLValT<VT>::T LT;
   typedef typename TLVals<VT>::Raw Raw;
   const int lane = threadIdx.x & 63;
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int w = NW == 1 ? 0 : __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // NW == 1: see tl_stream_ring
   const int nr = n_hi - n_lo;
   const int r0 = n_lo + (nr * w) / NW, r1 = n_lo + (nr * (w + 1)) / NW;
   if (r0 >= r1) return;
@@ -1201,6 +1207,114 @@ __global__ __launch_bounds__(NW * 64) void tl_fwd_multi_kernel(const int* __rest
                                               (const VT*)pc[1], nar, x + q[5], a, stats, acc, red);
 }
 
+// TALL forward units (ops/tiled.py, "tall forward units"): 2^12 rows = 4 sub-blocks of 1024 rows. The narrow
+// sections are the sub-blocks' own (16-bit packs, 10 slot bits); the wide entries of the 4 sub-blocks are ONE
+// section sorted by (column, row in unit) with 12 slot bits, so a tail gather instruction reads the columns of
+// four times as many rows and touches fewer distinct cache lines. One work-group of 4 waves and ONE fp64
+// accumulator row acc[4096] (32 KB: 5 work-groups per CU), no per-wave copies:
+//   phase 1: wave w walks ALL narrow rounds [n_w, n_w+1) of sub-block w into acc + 1024 w (disjoint slots);
+//   phase 2: after a barrier, wave 0 alone walks the wide section in stored order into acc (the other waves wait
+//            at the next barrier; the CU's other work-groups are in other phases meanwhile).
+// Deterministic by the argument of the TILED LAYOUT block: every slot is added to by one wave at a time, in
+// program order; per row: its narrow entries in sorted order, then its tail entries in sorted order.
+// PT: the ring pipeline of phase 2 (3 / 5 / 6 as in tl_stream). Finish and FWD_* modes as in tl_fwd_block; one stats
+// pair per non-empty SUB-BLOCK, summed as tl_fwd_block sums a 1024-row block's (see the finish loop).
+#define TL_TALL_BITS 12
+#define TL_TALL_SUB 10
+template <typename VT, typename XT, typename RT, int PT>
+__device__ __forceinline__ void tl_fwd_tall_block(int row_lo, int nrows, int e_lo, int e_hi,
+                                                  const int* __restrict__ nq /* {n_lo, n_hi, n1, n2, n3, sb} */,
+                                                  const uint32_t* __restrict__ pack, const VT* __restrict__ val,
+                                                  const TLNarrow& nar, const XT* __restrict__ x,
+                                                  const FwdArgs<XT, RT>& a, double* __restrict__ stats, double* acc) {
+  constexpr int NW = 4;
+  for (int i = threadIdx.x; i < (1 << TL_TALL_BITS); i += NW * 64) acc[i] = 0.0;
+  __syncthreads();
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int n_lo = w == 0 ? nq[0] : nq[1 + w], n_hi = w == NW - 1 ? nq[1] : nq[2 + w];   // scalar loads
+  if (n_hi > n_lo)
+    tl_narrow<VT, XT, double, false, 1, (PT >= 5 ? 4 : 2)>(nar, n_lo, n_hi, TL_TALL_SUB, x, acc + (w << TL_TALL_SUB));
+  __syncthreads();
+  if (w == 0) {
+    if (PT == 6) tl_stream_ring<VT, XT, double, false, 1, 5, 2>(pack, val, x, e_lo, e_hi, TL_TALL_BITS, acc, nar.wbase);
+    else if (PT == 5) tl_stream_ring<VT, XT, double, false, 1, 3, 1>(pack, val, x, e_lo, e_hi, TL_TALL_BITS, acc, nar.wbase);
+    else tl_stream_ring<VT, XT, double, false, 1, 2, 0>(pack, val, x, e_lo, e_hi, TL_TALL_BITS, acc, nar.wbase);
+  }
+  __syncthreads();
+  // Finish and stats PER SUB-BLOCK, in the order of a 1024-row block of tl_fwd_block<.., NW = 2>: waves 2p and 2p + 1
+  // are the two waves of sub-blocks 2p and 2p + 1 (thread t of 128 takes rows t, t + 128, ...; wave sums; wave 0's
+  // sum + wave 1's). The (F, S) pairs and their number are then those of the row-block layout, so the loss and
+  // sum l' of a shard do not depend on the unit height (reduce_stats groups the pairs by their count).
+  const int t = ((w & 1) << 6) | (threadIdx.x & 63);
+  double Fk[2], Sk[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int k0 = ((w >> 1) * 2 + j) << TL_TALL_SUB;
+    const int nk = min(nrows - k0, 1 << TL_TALL_SUB);
+    double F = 0.0, S = 0.0;
+    for (int r = k0 + t; r < k0 + nk; r += 128) {
+      const int s = row_lo + r;
+      fwd_finish(a, s, acc[r], fwd_prefetch(a, s), F, S);
+    }
+    Fk[j] = F; Sk[j] = S;
+  }
+  if (stats) {
+    const int sb = nq[5];             // stats index of the unit's first sub-block
+#pragma unroll
+    for (int j = 0; j < 2; ++j) { Fk[j] = wave_sum(Fk[j]); Sk[j] = wave_sum(Sk[j]); }
+    __syncthreads();                  // acc doubles as the reduction scratch: this barrier follows its last read
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {   // {F, S} of wave (w & 1) of sub-block k at acc[4 k + 2 (w & 1)]
+        const int k = (w >> 1) * 2 + j;
+        acc[4 * k + 2 * (w & 1)] = Fk[j]; acc[4 * k + 2 * (w & 1) + 1] = Sk[j];
+      }
+    }
+    __syncthreads();
+    const int k = threadIdx.x;
+    if (k < 4 && (k << TL_TALL_SUB) < nrows) {
+      double F = 0.0, S = 0.0;
+      for (int i = 0; i < 2; ++i) { F += acc[4 * k + 2 * i]; S += acc[4 * k + 2 * i + 1]; }
+      stats[2 * (sb + k)] = F; stats[2 * (sb + k) + 1] = S;
+    }
+  }
+}
+
+// blk: 10 ints per tall unit {row_lo, nrows, e_lo, e_hi, n_lo, n_hi, n1, n2, n3, sb}: sub-block k's narrow rounds
+// are [n_k, n_k+1) with n_0 = n_lo, n_4 = n_hi (a chunk's narrow rounds are stored sub-block by sub-block); its
+// stats pair is number sb + k (sb = 4 x the unit's index in the chunk).
+template <typename VT, typename XT, typename RT, int PT>
+__global__ __launch_bounds__(256) void tl_fwd_tall_kernel(const int* __restrict__ blk,
+                                                           const uint32_t* __restrict__ pack,
+                                                           const VT* __restrict__ val, TLNarrow nar,
+                                                           const XT* __restrict__ x, FwdArgs<XT, RT> a,
+                                                           double* __restrict__ stats,
+                                                           const unsigned char* __restrict__ live) {
+  __shared__ double acc[1 << TL_TALL_BITS];   // exactly 32 KB: a sixth array would cost the fifth work-group per CU
+  const int b = blockIdx.x;
+  if (live && !live[b]) return;
+  const int* q = blk + 10 * b;
+  tl_fwd_tall_block<VT, XT, RT, PT>(q[0], q[1], q[2], q[3], q + 4, pack, val, nar, x, a, stats, acc);
+}
+
+// Shard-wide: 12 ints per tall unit {chunk, global row_lo, nrows, e_lo, e_hi, col_lo, n_lo, n_hi, n1, n2, n3, sb}
+// (sb: the shard-wide number of the unit's first stats pair); stream pointers as in tl_fwd_multi_kernel.
+template <typename VT, typename XT, typename RT, int PT>
+__global__ __launch_bounds__(256) void tl_fwd_tall_multi_kernel(const int* __restrict__ blk,
+                                                                 const unsigned long long* __restrict__ ptrs,
+                                                                 const XT* __restrict__ x, FwdArgs<XT, RT> a,
+                                                                 double* __restrict__ stats,
+                                                                 const unsigned char* __restrict__ live) {
+  __shared__ double acc[1 << TL_TALL_BITS];   // exactly 32 KB: a sixth array would cost the fifth work-group per CU
+  const int b = blockIdx.x;
+  if (live && !live[b]) return;
+  const int* q = blk + 12 * b;
+  const unsigned long long* pc = ptrs + 6 * q[0];
+  const TLNarrow nar = {(const uint16_t*)pc[2], (const void*)pc[3], (const int*)pc[4], (const int*)pc[5]};
+  tl_fwd_tall_block<VT, XT, RT, PT>(q[1], q[2], q[3], q[4], q + 6, (const uint32_t*)pc[0], (const VT*)pc[1], nar,
+                                    x + q[5], a, stats, acc);
+}
+
 // Transpose over column-tile items. items: 4 ints {tile, e_lo, e_hi, part}; part < 0: the item is its tile's
 // only one -> G[tile cols] += sums directly; else the item's row of partial sums goes to parts[part * C ...].
 template <typename VT, typename XT, typename AT, bool SQ, int MAXR, int U, int NW, int P>
@@ -1330,11 +1444,12 @@ __global__ __launch_bounds__(NTHREADS) void tl_t_combine2_kernel(const int* __re
 
 // ``il``: 1 = the streams are stored in the lane-interleaved layout (see tl_stream_il) -> pipeline P = 3.
 // live: optional per-block flags (0 = skip the block: rows of converged entities in a block-diagonal problem)
+// tbits: 12 = ``blk`` holds tall units (tl_fwd_tall_kernel; rbits = 10, the sub-block bits), 0 = row blocks
 struct TLFwdDesc { const int* blk; int nblk; int rbits; const uint32_t* pack; const void* val; int il; TLNarrow nar;
-                  const unsigned char* live; };
+                  const unsigned char* live; int tbits; };
 // ptrs: 6 stream pointers per chunk (see tl_fwd_multi_kernel)
 struct TLFwdMultiDesc { const int* blk; int nblk; int rbits; const unsigned long long* ptrs; int il;
-                       const unsigned char* live; };
+                       const unsigned char* live; int tbits; };
 struct TLTDesc {
   const int* items; int nitems; int cbits; const uint32_t* pack; const void* val;
   const int* mt_tiles; const int* mt_ptr; int nmt; int dim;
@@ -1465,9 +1580,39 @@ static void tl_with_pipe(int il, int waves, int deep, int pipe, F f) {
   }
 }
 
+// Tall forward units: f(integral_constant<int, PT>) with the ring pipeline of the wide phase. Production: TL_TALL_P,
+// the depth chosen by the A/B of profiles/tl_tall_forward.md; the experiment build takes the tl_deep knob (0 / 1 / 2
+// -> P = 3 / 5 / 6). -22: a descriptor the tall kernels cannot run (fp64 data, plain order, other unit heights).
+#define TL_TALL_P 6
+template <typename XT, typename F>
+static int tl_with_tall(int tbits, int rbits, int il, F f) {
+  if constexpr (sizeof(XT) == 8) {
+    return -22;
+  } else {
+    if (tbits != TL_TALL_BITS || rbits != TL_TALL_SUB || !il) return -22;
+    if constexpr (TL_EXPERIMENT) {
+      if (g_tl_deep == 2) f(std::integral_constant<int, 6>{});
+      else if (g_tl_deep) f(std::integral_constant<int, 5>{});
+      else f(std::integral_constant<int, 3>{});
+    } else {
+      f(std::integral_constant<int, TL_TALL_P>{});
+    }
+    return 0;
+  }
+}
+
 template <typename VT, typename XT, typename RT>
 static int tl_fwd_impl(const TLFwdDesc* c, const void* x, FwdArgs<XT, RT> a, double* stats, hipStream_t st) {
   if (c->nblk <= 0) return 0;
+  if (c->tbits) {
+    const int rt = tl_with_tall<XT>(c->tbits, c->rbits, c->il, [&](auto pt) {
+      hipLaunchKernelGGL((tl_fwd_tall_kernel<VT, XT, RT, decltype(pt)::value>), dim3(c->nblk), dim3(256), 0, st,
+                         c->blk, c->pack, (const VT*)c->val, c->nar, (const XT*)x, a, stats, c->live);
+    });
+    if (rt) return rt;
+    LAUNCH_CHECK();
+    return 0;
+  }
   const int rc = tl_with_acc<XT>(c->rbits, [&](auto acc) {
     tl_with_pipe<2, 1>(c->il, g_tl_waves, g_tl_deep, g_tl_pipe, [&](auto pipe) {
       using A = decltype(acc); using Q = decltype(pipe);
@@ -1485,6 +1630,15 @@ template <typename VT, typename XT, typename RT>
 static int tl_fwd_multi_impl(const TLFwdMultiDesc* c, const void* x, FwdArgs<XT, RT> a, double* stats,
                              hipStream_t st) {
   if (c->nblk <= 0) return 0;
+  if (c->tbits) {
+    const int rt = tl_with_tall<XT>(c->tbits, c->rbits, c->il, [&](auto pt) {
+      hipLaunchKernelGGL((tl_fwd_tall_multi_kernel<VT, XT, RT, decltype(pt)::value>), dim3(c->nblk), dim3(256), 0,
+                         st, c->blk, c->ptrs, (const XT*)x, a, stats, c->live);
+    });
+    if (rt) return rt;
+    LAUNCH_CHECK();
+    return 0;
+  }
   const int rc = tl_with_acc<XT>(c->rbits, [&](auto acc) {
     tl_with_pipe<2, 2>(c->il, g_tl_waves, g_tl_deep, g_tl_pipe, [&](auto pipe) {
       using A = decltype(acc); using Q = decltype(pipe);

@@ -28,7 +28,7 @@ import torch
 from ..data.matrix import LabeledData
 from .native import SegChunkDesc, check, require_glm_lib, stream_handle
 from .reference import GLMComputable
-from .tiled import DEFAULT_ITEM_ENTRIES, TLFwdChunk, TLTChunk, tl_supported
+from .tiled import DEFAULT_ITEM_ENTRIES, TLFwdChunk, TLTChunk, shard_tall, tl_supported
 from ..utils.timing import phase, trace_range
 
 # Set after a tiled build's host -> device upload: GameData.prefetch_shard's copy waits for it, so the two copies do
@@ -225,7 +225,7 @@ class DeviceGLMData(GLMComputable):
             m = self.row_starts[c + 1] - self.row_starts[c]
             b = f.blk.cpu().to(torch.int64)
             if f.nblk and (int(b[:, 0].min()) < 0 or int((b[:, 0] + b[:, 1]).max()) > m
-                           or int(b[:, 1].max()) > (1 << f.rbits)):
+                           or int(b[:, 1].max()) > (1 << f.ubits)):
                 raise ValueError(f"chunk {c}: forward block rows out of range")
             q = 256 if f.il else 4   # the kernels read whole rounds (il) / whole quads
             end = b[:, 2] + (b[:, 3] - b[:, 2] + q - 1) // q * q if f.il else (b[:, 3] + 3) // 4 * 4
@@ -240,11 +240,11 @@ class DeviceGLMData(GLMComputable):
             wb = getattr(f, "wbase", None)
             if wb is not None and wb.numel() and int(wb.min()) < 0:
                 raise ValueError(f"chunk {c}: negative wide-round base")
-            if p.numel() and int((p >> f.rbits).max()) >= ncols:
+            if p.numel() and int((p >> f.ubits).max()) >= ncols:
                 raise ValueError(f"chunk {c}: forward gather index >= column window")
             counts = f.unit_counts().cpu()
             blk_rows = torch.repeat_interleave(b[:, 1], counts)
-            if p.numel() and bool(((p & ((1 << f.rbits) - 1)) >= blk_rows).any()):
+            if p.numel() and bool(((p & ((1 << f.ubits) - 1)) >= blk_rows).any()):
                 raise ValueError(f"chunk {c}: forward LDS slot >= block rows")
             it = t.items.cpu().to(torch.int64)
             if t.nitems:
@@ -376,7 +376,7 @@ class DeviceGLMData(GLMComputable):
                 rp = torch.from_numpy((xc.indptr - xc.indptr[0]).astype(np.int64)).to(dev)
                 col = torch.from_numpy(xc.indices.astype(np.int64)).to(dev)
                 val = torch.from_numpy(xc.data.astype(np.float64)).to(dev).to(vdt)
-                csr.append(TLFwdChunk(rp, col, val, dc))
+                csr.append(TLFwdChunk(rp, col, val, dc, tall=shard_tall(dmax, min(chunk_rows, n))))
                 csc.append(TLTChunk(rp, col, val, dc, chunk_rows, cbits=cbits, item_entries=item_entries))
                 continue
             sp_ = (xc.indptr - xc.indptr[0]).astype(np.int32)
@@ -438,9 +438,11 @@ class DeviceGLMData(GLMComputable):
     @staticmethod
     def from_device_csr(indptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, y, offsets, weights, dim: int,
                         device="cuda", precision: str = "f64", chunk_rows: int = 1 << 20,
-                        item_entries: Optional[int] = None, col_windows: bool = False):
+                        item_entries: Optional[int] = None, col_windows: bool = False,
+                        tall: Optional[bool] = None):
         """Tiled-layout shard built from device-resident CSR arrays: chunking, column windows, the forward
-        block sort and the transpose tile sort all run on the device (no host round trip of the non-zeros)."""
+        block sort and the transpose tile sort all run on the device (no host round trip of the non-zeros).
+        ``tall``: force the forward copies' tall units on / off (``tiled.TLFwdChunk``; None: the shard rule)."""
         dev = torch.device(device)
         vdt = VAL_DTYPE[PRECISIONS[precision]]
         indptr = indptr.to(dev, torch.int64)
@@ -474,7 +476,8 @@ class DeviceGLMData(GLMComputable):
             rp = indptr[a:b + 1] - ea
             c = col[ea:eb] - lo if lo else col[ea:eb]
             v = val[ea:eb].to(dev).to(vdt)
-            csr.append(TLFwdChunk(rp, c, v, hi - lo))
+            csr.append(TLFwdChunk(rp, c, v, hi - lo,
+                                  tall=shard_tall(dmax, min(chunk_rows, n)) if tall is None else tall))
             csc.append(TLTChunk(rp, c, v, hi - lo, chunk_rows, cbits=cbits, item_entries=item_entries))
             col_lo.append(lo)
             del c, v
@@ -543,11 +546,11 @@ class DeviceGLMData(GLMComputable):
             nb = self._multi_blk.clone()
             cb = torch.cat([ch.blk for ch in view.csr])
             nb[:, 3:5] = cb[:, 2:4]
-            nb[:, 6:8] = cb[:, 4:6]
+            nb[:, 6:6 + min(cb.shape[1], 9) - 4] = cb[:, 4:9]   # narrow ranges (tall units: the sub-blocks' too)
             view._multi_blk = nb
             view._multi_ptrs = stream_ptr_table(view.csr, self.device)
             view._multi = TLFwdMultiDesc(nb.data_ptr(), nb.shape[0], self._multi.rbits, view._multi_ptrs.data_ptr(),
-                                         self._multi.il)
+                                         self._multi.il, tbits=self._multi.tbits)
         view._multi_t = None if self._multi_t is None else self._multi_t.restreamed(view.csc)
         gb = getattr(self, "_gbuckets", None)
         if gb is not None and gb[1] is not None:
@@ -940,19 +943,23 @@ class DeviceGLMData(GLMComputable):
 
     def _build_multi(self):
         """One-launch forward over all TL chunks (block table {chunk, row_lo, nrows, e_lo, e_hi, col_lo, n_lo,
-        n_hi})."""
+        n_hi}; tall units: {..., n_lo, n_hi, n1, n2, n3, sb}, the chunk tables' extra columns, sb: a unit's first stats
+        pair counted over the shard)."""
         self._multi = None
-        if not self.csr or any(ch.kind != "tl" for ch in self.csr) or len({ch.rbits for ch in self.csr}) != 1:
+        if (not self.csr or any(ch.kind != "tl" for ch in self.csr) or len({ch.rbits for ch in self.csr}) != 1
+                or len({ch.tbits for ch in self.csr}) != 1):
             return
         tabs = []
         for c, ch in enumerate(self.csr):
             b = ch.blk.to(torch.int64)
-            t = torch.empty((b.shape[0], 8), dtype=torch.int64, device=b.device)
+            t = torch.empty((b.shape[0], b.shape[1] + 2), dtype=torch.int64, device=b.device)
             t[:, 0] = c
             t[:, 1] = b[:, 0] + self.row_starts[c]
             t[:, 2:5] = b[:, 1:4]
             t[:, 5] = self.col_lo[c]
-            t[:, 6:8] = b[:, 4:6]
+            t[:, 6:] = b[:, 4:]
+            if ch.tbits:
+                t[:, 11] += self.blk_off[c]
             tabs.append(t)
         self._multi_blk = torch.cat(tabs).to(torch.int32).contiguous()
         from .tiled import stream_ptr_table
@@ -961,7 +968,7 @@ class DeviceGLMData(GLMComputable):
         if len({ch.il for ch in self.csr}) != 1:
             return
         self._multi = TLFwdMultiDesc(self._multi_blk.data_ptr(), self._multi_blk.shape[0], self.csr[0].rbits,
-                                     self._multi_ptrs.data_ptr(), self.csr[0].il)
+                                     self._multi_ptrs.data_ptr(), self.csr[0].il, tbits=self.csr[0].tbits)
 
     def _build_multi_t(self):
         """One-launch transpose over all chunks. Column-window chunks (block-diagonal random-effect problems) take

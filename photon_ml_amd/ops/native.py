@@ -40,14 +40,19 @@ class TLNarrow(ctypes.Structure):
 
 
 class TLFwdDesc(ctypes.Structure):
+    """``tbits`` = 12: ``blk`` is a table of tall units (10 ints per unit: {row_lo, nrows, e_lo, e_hi, n_lo, n_hi, n1,
+    n2, n3, sb}, the narrow rounds of sub-block k = [n_k, n_k+1) with n_0 = n_lo and n_4 = n_hi, its stats pair
+    number sb + k; ``rbits`` = 10, the sub-block bits); 0: row blocks of ``2^rbits`` rows, 6 ints each (ops/tiled.py)."""
     _fields_ = [("blk", c_void_p), ("nblk", c_int), ("rbits", c_int), ("pack", c_void_p), ("val", c_void_p),
-                ("il", c_int), ("nar", TLNarrow), ("live", c_void_p)]
+                ("il", c_int), ("nar", TLNarrow), ("live", c_void_p), ("tbits", c_int)]
 
 
 class TLFwdMultiDesc(ctypes.Structure):
-    """``ptrs``: 5 stream pointers per chunk {pack, val, narrow pack, narrow val, narrow base}."""
+    """``ptrs``: 6 stream pointers per chunk {pack, val, narrow pack, narrow val, narrow base, wide-round bases}.
+    ``tbits`` = 12: tall units, 12 ints per unit {chunk, row_lo, nrows, e_lo, e_hi, col_lo, n_lo, n_hi, n1, n2, n3,
+    sb}; 0: 8 ints per row block."""
     _fields_ = [("blk", c_void_p), ("nblk", c_int), ("rbits", c_int), ("ptrs", c_void_p), ("il", c_int),
-                ("live", c_void_p)]
+                ("live", c_void_p), ("tbits", c_int)]
 
 
 class TLTMultiDesc(ctypes.Structure):
@@ -62,7 +67,7 @@ class CmpArgs(ctypes.Structure):
                 ("sbits", c_int), ("key_is_row", c_int), ("pack", c_void_p), ("val", c_void_p),
                 ("npack", c_void_p), ("nval", c_void_p), ("nbase", c_void_p), ("keep", c_void_p),
                 ("seg_cnt", c_void_p), ("seg_first", c_void_p), ("unit_lo", c_void_p), ("opack", c_void_p),
-                ("oval", c_void_p)]
+                ("oval", c_void_p), ("ustride", c_int), ("wbits", c_int)]
 
 
 class SegRankArgs(ctypes.Structure):

@@ -29,6 +29,22 @@ Same entries in the same order; a narrow round then costs one 16-byte stream loa
 ones. ``npack`` / ``nval`` of such a chunk are strided views into the record stream ``nrec`` and the kernels get a
 null narrow-value pointer. fp32 / fp64 chunks (16-byte value quads already) keep the two arrays.
 
+TALL FORWARD UNITS (``PML_TL_TALL=0/1``; by default bf16 / fp32 shards in the interleaved + narrow layout with
+``dim >= 2^16`` and chunks of at least 4096 rows; fp64 shards keep the row blocks above): a forward chunk is cut
+into units of ``2^tbits = 4096`` rows, each 4 SUB-BLOCKS of ``2^rbits = 1024`` rows (the last unit and its last
+sub-block may be ragged). The narrow section is built per sub-block exactly as above (same split rule, 16-bit packs
+``((key - base) << 10) | row_in_sub_block``, same records and bases; a chunk's narrow rounds are stored sub-block
+by sub-block). The entries that stay wide are MERGED per unit: one wide section sorted by (column, row in unit),
+packed ``(col << 12) | row12``, lane-interleaved and padded to whole rounds per unit (``dim > 2^20``: keys relative
+to the per-round bases ``wbase``). Entries are moved, not duplicated, and four blocks' pad rounds become one. A
+tail gather instruction then reads the columns of four times as many rows: 0.40 instead of 0.53 distinct 64-byte
+lines per wide entry at the bench shape (``scripts/tl_tail_lines.py``). Unit table: 10 ints ``{row_lo, nrows, e_lo,
+e_hi, n_lo, n_hi, n1, n2, n3, sb}`` -- the narrow rounds of sub-block k are ``[n_k, n_k+1)`` with ``n_0 = n_lo`` and
+``n_4 = n_hi``. ``nstats`` is one (loss, sum l') pair per non-empty SUB-BLOCK, number ``sb + k`` with ``sb`` = 4 x
+the unit's index: the kernel sums a sub-block's pair exactly as the row-block kernel sums a 1024-row block's, so a
+shard's loss does not depend on the unit height, bit for bit. The kernel (``tl_fwd_tall_block``) keeps ONE fp64 accumulator row of
+4096 slots per work-group: wave k walks sub-block k's narrow rounds, then one wave walks the wide section.
+
 Both copies are stored LANE-INTERLEAVED by default (``il``; ``PML_TL_IL=0`` keeps the plain order): every work
 unit (forward block / transpose item) starts on a 256-entry round boundary and is zero-padded to whole rounds,
 and inside a round the 16-B quad of lane L holds the unit's sorted entries L, L+64, L+128, L+192, so each gather
@@ -100,6 +116,14 @@ NARROW = int(os.environ.get("PML_TL_NARROW", "1"))
 NARROW_W = 64            # key window loaded per narrow round (one wave64 load)
 FUSE = int(os.environ.get("PML_TL_FUSE", "1"))   # bf16 narrow rounds as fused 16-byte lane records
 WIDE_BASE = int(os.environ.get("PML_TL_WIDE_BASE", "1"))   # per-round key bases for wide shards (TLFwdChunk)
+# Tall forward units (TLFwdChunk, "TALL FORWARD UNITS" above): PML_TL_TALL=0/1 overrides the engagement rule.
+TALL = os.environ.get("PML_TL_TALL")
+TALL = None if TALL is None else bool(int(TALL))
+TALL_DEFAULT = True      # the rule engages on its own (False: only PML_TL_TALL=1 / the constructor argument)
+TALL_BITS = 12           # rows of a tall unit (2^12 fp64 sums = 32 KB of LDS per work-group)
+TALL_SUB_BITS = 10       # rows of its sub-blocks: the slot bits of the narrow rounds' 16-bit packs
+TALL_MIN_DIM = 1 << 16
+TALL_COLS = 10           # ints per row of a tall unit table
 
 
 def narrow_width(sbits: int) -> int:
@@ -182,13 +206,14 @@ def il_phys(e_lo: torch.Tensor, n: torch.Tensor) -> torch.Tensor:
     return e_lo[unit] + (j - t) + ((t & 63) << 2) + (t >> 6)
 
 
-def _interleave(pack: torch.Tensor, val: torch.Tensor, n: torch.Tensor):
+def _interleave(pack: torch.Tensor, val: torch.Tensor, n: torch.Tensor, tail: int = _PAD):
     """Lane-interleave sorted streams whose units are consecutive runs of ``n`` entries. Returns the padded
-    streams and the new (round-aligned) unit starts."""
+    streams and the new (round-aligned) unit starts. ``tail``: spare entries after the last round (the interleaved
+    readers stay inside whole rounds, so 0 is safe for them)."""
     n = n.to(torch.int64)
     padded = (n + IL_ROUND - 1) // IL_ROUND * IL_ROUND
     new_lo = torch.cumsum(padded, 0) - padded
-    total = int(padded.sum()) + _PAD
+    total = int(padded.sum()) + tail
     phys = il_phys(new_lo, n)
     p = torch.zeros(total, dtype=pack.dtype, device=pack.device)
     v = torch.zeros(total, dtype=val.dtype, device=val.device)
@@ -330,13 +355,40 @@ class _NarrowMixin:
         return pk, vl
 
 
+def tall_engages(tall: Optional[bool], dim: int, m: int, dtype, il: int, want_rbits: int) -> bool:
+    """Whether a forward chunk of ``m`` rows is built with tall units. The layout can hold bf16 / fp32 chunks in the
+    interleaved + narrow layout with 1024-row sub-blocks (fp64 shards keep their own block policy). Forced by
+    ``tall`` (constructor) or ``PML_TL_TALL``; else wide feature spaces (``dim >= 2^16``: below, the whole
+    coefficient vector is a few hundred cache lines and the tail gathers are cheap already) and chunks of at least
+    one full unit."""
+    if not (il and NARROW and dtype != torch.float64 and want_rbits == TALL_SUB_BITS):
+        return False
+    if tall is None:
+        tall = TALL
+    if tall is None:
+        tall = TALL_DEFAULT and dim >= TALL_MIN_DIM and m >= (1 << TALL_BITS)
+    return bool(tall)
+
+
+def shard_tall(dim: int, chunk_rows: int) -> Optional[bool]:
+    """One choice for every chunk of a shard (the shard-wide forward launch needs one unit height): the rule applied
+    to the shard's widest column window and to its full chunks, so a short last chunk follows the others (a ragged
+    tall unit). None (each chunk's own rule) when ``PML_TL_TALL`` decides anyway."""
+    if TALL is not None:
+        return None
+    return bool(TALL_DEFAULT and dim >= TALL_MIN_DIM and chunk_rows >= (1 << TALL_BITS))
+
+
 class TLFwdChunk(_NarrowMixin):
     """Forward copy of one row chunk (``m`` rows)."""
 
     kind = "tl"
 
     def __init__(self, rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, dim: int,
-                 rbits: Optional[int] = None, il: Optional[int] = None):
+                 rbits: Optional[int] = None, il: Optional[int] = None, tall: Optional[bool] = None):
+        """``tall``: True / False force the tall-unit layout on / off (where the layout can hold the chunk at all:
+        bf16 / fp32 values, interleaved + narrow, 1024-row sub-blocks); None: ``PML_TL_TALL``, else the rule of
+        :func:`tall_engages`."""
         dev = val.device
         self.il = INTERLEAVE if il is None else int(il)
         rowptr = rowptr.to(dev, torch.int64)
@@ -349,6 +401,9 @@ class TLFwdChunk(_NarrowMixin):
         # wide shards: (col << rbits) would overflow 32 bits at the wanted block size -> keys relative to one base
         # per wide round (the full block size instead of 2^(32 - bits(D)) rows; see tl_stream_ring)
         want = _cap(default_rbits(dim, f64) if rbits is None else rbits, f64)
+        self.tbits = 0
+        if tall_engages(tall, dim, m, val.dtype, self.il, want) and self._init_tall(rowptr, col, val, dim, m):
+            return
         use_base = bool(self.il) and WIDE_BASE and want > self.rbits
         if use_base:
             self.rbits = want
@@ -375,7 +430,7 @@ class TLFwdChunk(_NarrowMixin):
                 wp = self._rebase(wp, wn)
                 if wp is None:      # a wide round spans more keys than 32 - rbits bits: plain packs, fewer rows
                     del wv, npk, nvl, nbs
-                    self.__init__(rowptr, col, val, dim, fwd_bits(dim, f64, rbits), il)
+                    self.__init__(rowptr, col, val, dim, fwd_bits(dim, f64, rbits), il, tall=False)
                     return
             self.pack, self.val, e_lo = _interleave(_to_u32_bits(wp), wv, wn)
             e_hi = e_lo + wn
@@ -394,11 +449,74 @@ class TLFwdChunk(_NarrowMixin):
         self.desc = TLFwdDesc(self.blk.data_ptr(), nblk, self.rbits, self.pack.data_ptr(), self.val.data_ptr(),
                               self.il, self.nar)
 
-    def _rebase(self, wp: torch.Tensor, wn: torch.Tensor) -> Optional[torch.Tensor]:
-        """Wide packs (int64 ``(key << rbits) | slot``, units of ``wn`` sorted entries) relative to the first key of
-        their round of the interleaved layout; sets ``self.wbase`` (int32 per physical round). None when some
-        round's key span does not fit 32 - rbits bits."""
+    def _init_tall(self, rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, dim: int, m: int) -> bool:
+        """The tall-unit layout (module docstring, TALL FORWARD UNITS). False: some wide round of a shard with
+        per-round bases spans more keys than 32 - 12 bits, nothing was set and the caller builds today's layout."""
+        dev = val.device
+        S, T = TALL_SUB_BITS, TALL_BITS
+        cb = _bits(dim)
+        nnz = col.numel()
+        rows = torch.repeat_interleave(torch.arange(m, device=dev), rowptr[1:] - rowptr[:-1]) if nnz else \
+            torch.zeros(0, dtype=torch.int64, device=dev)
+        # narrow sections: per 1024-row sub-block, exactly as in the plain layout
+        key = ((rows >> S) << (cb + S)) | (col << S) | (rows & ((1 << S) - 1))
+        del rows
+        key, perm = torch.sort(key, stable=True)
+        nunit = (m + (1 << T) - 1) >> T
+        nsub = nunit << (T - S)                               # sub-block slots; those past the last row are empty
+        slo = torch.clamp(torch.arange(nsub, device=dev) << S, max=m)
+        cnt = rowptr[torch.clamp(slo + (1 << S), max=m)] - rowptr[slo]
+        wp, wv, wn, npk, nvl, nbs, nr = split_narrow(key & ((1 << (cb + S)) - 1), val[perm], cnt, S, dim)
+        del key, perm
+        # wide section: the wide entries of a unit's sub-blocks merged and sorted by (column, row in unit)
+        # (the entries arrive sorted by (sub-block, column, row), so a STABLE sort by (unit, column) alone leaves them
+        # in (unit, column, sub-block, row) = (unit, column, row in unit) order: a 32-bit key at the bench shape, half
+        # the radix passes of the full 64-bit key)
+        sub = torch.repeat_interleave(torch.arange(nsub, device=dev), wn)
+        tp = ((wp >> S) << T) | ((sub & ((1 << (T - S)) - 1)) << S) | (wp & ((1 << S) - 1))
+        ukey = ((sub >> (T - S)) << cb) | (wp >> S)
+        del sub, wp
+        if _bits(max(nunit, 1)) + cb <= 31:
+            ukey = ukey.to(torch.int32)
+        tperm = torch.sort(ukey, stable=True).indices
+        del ukey
+        tp, wv = tp[tperm], wv[tperm]
+        del tperm
+        un = wn.view(nunit, -1).sum(1)
+        if cb + T > 32:
+            tp = self._rebase(tp, un, T) if WIDE_BASE else None
+            if tp is None:
+                self.wbase = None
+                return False
+        self.rbits, self.tbits = S, T
+        # (no spare quad after the last round: tall chunks are interleaved only, and the 16 bytes a unit table row
+        # gains over a row block's must not make a one-sub-block chunk larger than the plain layout's)
+        self.pack, self.val, e_lo = _interleave(_to_u32_bits(tp), wv, un, tail=0)
+        del tp, wv
+        nh = torch.cumsum(nr, 0)
+        nl = (nh - nr).view(nunit, -1)
+        ulo = torch.arange(nunit, device=dev) << T
+        self._sbits, self._ew = S, (2, 3)
+        self._set_narrow(npk, nvl, nbs)
+        self.blk = torch.stack([ulo, torch.clamp(ulo + (1 << T), max=m) - ulo, e_lo, e_lo + un, nl[:, 0],
+                                nh.view(nunit, -1)[:, -1], nl[:, 1], nl[:, 2], nl[:, 3], ulo >> S],
+                               1).to(torch.int32).contiguous()
+        self.nblk, self.m, self.nnz = nunit, m, nnz
+        self.desc = TLFwdDesc(self.blk.data_ptr(), nunit, S, self.pack.data_ptr(), self.val.data_ptr(), 1, self.nar,
+                              tbits=T)
+        return True
+
+    @property
+    def ubits(self) -> int:
+        """Row bits of a unit of the table = slot bits of the wide packs and of :meth:`logical`'s packs."""
+        return self.tbits or self.rbits
+
+    def _rebase(self, wp: torch.Tensor, wn: torch.Tensor, bits: Optional[int] = None) -> Optional[torch.Tensor]:
+        """Wide packs (int64 ``(key << bits) | slot``, units of ``wn`` sorted entries; ``bits``: rbits unless given)
+        relative to the first key of their round of the interleaved layout; sets ``self.wbase`` (int32 per physical
+        round). None when some round's key span does not fit 32 - bits bits."""
         dev = wp.device
+        bits = self.rbits if bits is None else bits
         n = wn.to(torch.int64)
         tot = int(n.sum())
         padded = (n + IL_ROUND - 1) // IL_ROUND * IL_ROUND
@@ -409,21 +527,22 @@ class TLFwdChunk(_NarrowMixin):
             j = torch.arange(tot, device=dev) - (torch.cumsum(n, 0) - n)[unit]
             rid = ((torch.cumsum(padded, 0) - padded)[unit] + j) // IL_ROUND     # same rounds as _interleave
             del unit
-            key = wp >> self.rbits
+            key = wp >> bits
             first = (j % IL_ROUND) == 0
             del j
             wbase[rid[first]] = key[first]
             rel = key - wbase[rid]
             del rid, key, first
-            if int(rel.max()) >= 1 << (32 - self.rbits):
+            if int(rel.max()) >= 1 << (32 - bits):
                 return None
-            wp = (rel << self.rbits) | (wp & ((1 << self.rbits) - 1))
+            wp = (rel << bits) | (wp & ((1 << bits) - 1))
         self.wbase = wbase.to(torch.int32).contiguous()
         return wp
 
     @property
     def nstats(self) -> int:
-        return self.nblk
+        # tall units: one pair per non-empty sub-block (table column 9 holds a unit's first pair)
+        return (self.m + (1 << self.rbits) - 1) >> self.rbits if self.tbits else self.nblk
 
     parts_needed = 0
 
@@ -436,23 +555,41 @@ class TLFwdChunk(_NarrowMixin):
 
     def logical(self):
         """(pack, val) of the non-zeros in unit order (per block: its narrow entries, then its wide entries, each
-        sorted by column), whatever the storage order; packs as non-negative int64 ``(col << rbits) | row``."""
+        sorted by column), whatever the storage order; packs as non-negative int64 ``(col << ubits) | row`` (a tall
+        unit: its narrow entries sub-block by sub-block, ``row`` = the row in the unit)."""
         if not self.il:
             return self.pack[: self.nnz].to(torch.int64) & 0xFFFFFFFF, self.val[: self.nnz]
         ph = il_phys(self.blk[:, 2], self.blk[:, 3] - self.blk[:, 2])
         wp = self.pack[ph].to(torch.int64) & 0xFFFFFFFF
+        ub = self.ubits
         if self.wbase is not None:
-            wp = ((self.wbase[ph // IL_ROUND].to(torch.int64) + (wp >> self.rbits)) << self.rbits) | (
-                wp & ((1 << self.rbits) - 1))
-        return self._logical_all(wp, self.val[ph])
+            wp = ((self.wbase[ph // IL_ROUND].to(torch.int64) + (wp >> ub)) << ub) | (wp & ((1 << ub) - 1))
+        if not self.tbits:
+            return self._logical_all(wp, self.val[ph])
+        t = self.blk.to(torch.int64)
+        dev = wp.device
+        U = t.shape[0]
+        if not U or int((t[:, 5] - t[:, 4]).sum()) == 0:
+            return wp, self.val[ph]
+        S, T = self.rbits, self.tbits
+        # the narrow rounds of a chunk are stored sub-block by sub-block, so unit by unit: rounds [0, last n_hi)
+        npk, nvl = narrow_logical(self.npack, self.nval, self.nbase, 0, int(t[-1, 5]), S)
+        bounds = torch.stack([t[:, 4], t[:, 6], t[:, 7], t[:, 8], t[:, 5]], 1)
+        per_sub = (bounds[:, 1:] - bounds[:, :-1]).reshape(-1)
+        esub = torch.repeat_interleave(torch.arange(per_sub.numel(), device=dev), IL_ROUND * per_sub.to(dev))
+        npk = ((npk >> S) << T) | ((esub & ((1 << (T - S)) - 1)) << S) | (npk & ((1 << S) - 1))
+        unit = torch.cat([esub >> (T - S), torch.repeat_interleave(torch.arange(U, device=dev),
+                                                                   (t[:, 3] - t[:, 2]).to(dev))])
+        order = torch.sort(unit, stable=True).indices
+        return torch.cat([npk, wp])[order], torch.cat([nvl, self.val[ph]])[order]
 
     # host emulation of the kernel arithmetic (tests / CPU fallback)
     def emulate_matvec(self, x: torch.Tensor) -> torch.Tensor:
         pk, vl = self.logical()
         p = pk.to(torch.int64)
-        col = p >> self.rbits
+        col = p >> self.ubits
         blk_of_entry = torch.repeat_interleave(torch.arange(self.nblk, device=p.device), self.unit_counts())
-        row = (blk_of_entry << self.rbits) + (p & ((1 << self.rbits) - 1))
+        row = (blk_of_entry << self.ubits) + (p & ((1 << self.ubits) - 1))
         z = torch.zeros(self.m, dtype=torch.float64, device=p.device)
         return z.index_add_(0, row, vl.to(torch.float64) * x.to(torch.float64)[col])
 
@@ -775,7 +912,8 @@ class RowCompaction:
                             0 if forward else 1, ch.pack.data_ptr(), ch.val.data_ptr(), ch.npack.data_ptr(),
                             None if ch.fused else ch.nval.data_ptr(), ch.nbase.data_ptr(), keep.data_ptr(),
                             self.seg_cnt.data_ptr(),
-                            None, None, None, None)
+                            None, None, None, None, table.shape[1], getattr(ch, "ubits", ch._sbits) if forward
+                            else ch._sbits)
         self.lib, self.stream = require_game_lib(), stream_handle(dev)
         self.vbytes = ch.val.element_size()
         if S:
@@ -806,7 +944,7 @@ class RowCompaction:
         table[:, lo] = self.unit_lo
         table[:, hi] = self.unit_lo + self.unit_cnt
         if self.filter_narrow:
-            table[:, 4:6] = 0
+            table[:, 4:9] = 0            # (a tall unit table: its sub-blocks' first narrow rounds too; not column 9)
         table = table.to(torch.int32).contiguous()
         nc = copy.copy(ch)               # shares the narrow streams (npack / nval / nbase, table columns 4, 5)
         nc._cmp_seg = {}
@@ -818,7 +956,8 @@ class RowCompaction:
             nc.nnz = kept + self.n_narrow
         if self.forward:
             nc.blk = table
-            nc.desc = TLFwdDesc(table.data_ptr(), nc.nblk, nc.rbits, opack.data_ptr(), oval.data_ptr(), 1, nc.nar)
+            nc.desc = TLFwdDesc(table.data_ptr(), nc.nblk, nc.rbits, opack.data_ptr(), oval.data_ptr(), 1, nc.nar,
+                                tbits=nc.tbits)
         else:
             nc.items = table
             nc.desc = TLTDesc(table.data_ptr(), nc.nitems, nc.cbits, opack.data_ptr(), oval.data_ptr(),

@@ -53,6 +53,13 @@ def runtime_warmup(device, force: bool = False) -> float:
     x.to(torch.float32).to(torch.bfloat16)
     # our libraries: the first launch loads each module's code object
     check_lds_add_order(dev)                                             # libpml_glm
+    # the tall-unit forward family (tl_fwd_tall_*): one ragged unit of 8 rows x 2 entries, per-chunk and shard-wide
+    from .device import DeviceGLMData
+    tiny = DeviceGLMData.from_device_csr(torch.arange(0, 18, 2, device=dev), i[:16] % 5, x[:16].to(torch.float32),
+                                         torch.zeros(8), torch.zeros(8), torch.ones(8), 5, dev, "f32", tall=True)
+    tiny.matvec(torch.zeros(5, dtype=torch.float64, device=dev))
+    z = torch.zeros(8, dtype=torch.float64, device=dev)
+    tiny._fwd(0, torch.zeros(5, dtype=torch.float32, device=dev), 0, 0, 0.0, None, None, z_out=z, stats=False)
     key_histogram(i % 13, 13)                                            # libpml_game
     csr_gather_rows(torch.tensor([0, 2], dtype=torch.int64, device=dev), i[:2], x[:2],
                     torch.zeros(1, dtype=torch.int64, device=dev), torch.tensor([0, 4], dtype=torch.int64, device=dev))

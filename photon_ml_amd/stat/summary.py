@@ -111,7 +111,7 @@ class BasicStatisticalSummary:
         mn = torch.full((d,), float("inf"), dtype=f64, device=dev)
         for c, ch in enumerate(data.csr):
             pk, vl = ch.logical()
-            col = (pk.to(torch.int64) >> ch.rbits) + data.col_lo[c]     # logical(): non-negative int64
+            col = (pk.to(torch.int64) >> ch.ubits) + data.col_lo[c]     # logical(): non-negative int64
             v = vl.to(f64)
             s1.index_add_(0, col, v)
             s2.index_add_(0, col, v * v)
