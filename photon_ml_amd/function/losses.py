@@ -25,6 +25,12 @@ def log1p_exp(x: torch.Tensor) -> torch.Tensor:
     return torch.where(x > 0, x + torch.log1p(torch.exp(-x.abs())), torch.log1p(torch.exp(-x.abs())))
 
 
+def weighted(w: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+    """``w * t`` with an exact 0 where the row weight is 0, whatever the term (``wx`` in ``glm_kernels.hip``): a
+    zero-weight row whose ``exp`` overflowed must not turn 0 x inf into NaN."""
+    return torch.where(w != 0, w * t, torch.zeros_like(t))
+
+
 def log1p_exp_scalar(x: float) -> float:
     return x + math.log1p(math.exp(-x)) if x > 0 else math.log1p(math.exp(x))
 

@@ -2455,9 +2455,9 @@ __global__ __launch_bounds__(NTHREADS) void rs_tron_kernel(
     double l, dl, d2;
     pointwise_loss(loss, z, y, l, dl, d2);
     if (!on) { l = 0.0; dl = 0.0; d2 = 0.0; }
-    f = gsum(wt * l + 0.5 * l2 * v * v);
-    gr = mvt(wt * dl) + l2 * v;
-    Dw = wt * d2;
+    f = gsum(wx(wt, l) + 0.5 * l2 * v * v);
+    gr = mvt(wx(wt, dl)) + l2 * v;
+    Dw = wx(wt, d2);
   };
   const double eta0 = 1e-4, eta1 = 0.25, eta2 = 0.75, s1 = 0.25, s2 = 0.5, s3 = 4.0;
   double f, gr, Dw;
@@ -3027,9 +3027,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(rs_dpp_wpe<
       double l, dl, d2;
       pointwise_loss(loss, z[s] + off, y, l, dl, d2);
       if (!on[s]) { l = 0.0; dl = 0.0; d2 = 0.0; }
-      lt[s] = wt * l + 0.5 * l2 * v[s] * v[s];
-      cf[s] = wt * dl;
-      Dw[s] = wt * d2;
+      lt[s] = wx(wt, l) + 0.5 * l2 * v[s] * v[s];
+      cf[s] = wx(wt, dl);
+      Dw[s] = wx(wt, d2);
     }
     f = gsum(lt);
     mvt(cf, gr);

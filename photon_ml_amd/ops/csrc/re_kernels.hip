@@ -76,6 +76,10 @@ __device__ __forceinline__ void loss_t(double z, double y, double& l, double& dl
   }
 }
 
+// weight x per-row term with an exact 0 for zero-weight rows whatever the term (wx in glm_kernels.hip): a
+// zero-weight row whose exp overflowed (a partial score, an overshooting trial step) must not turn 0 x inf into NaN
+__device__ __forceinline__ double wx(double w, double x) { return w != 0.0 ? w * x : 0.0; }
+
 template <int CTRL>
 __device__ __forceinline__ double dpp_f64(double v) {
   const long long b = __builtin_bit_cast(long long, v);
@@ -289,11 +293,11 @@ __device__ __forceinline__ void row_pass(const ReTronArgs& a, long long r0, long
         if (valid) {
           loss_t<LOSS>(dot[u] + rs[u][1], rs[u][2], l, dl, d2);
           if (gl == 0) {
-            fpart += rs[u][0] * l;
-            if (MODE == 1) { Dn[i] = rs[u][0] * d2; Zn[i] = dot[u]; }
+            fpart += wx(rs[u][0], l);
+            if (MODE == 1) { Dn[i] = wx(rs[u][0], d2); Zn[i] = dot[u]; }
           }
         }
-        t = rs[u][0] * dl;
+        t = wx(rs[u][0], dl);
       }
 #pragma unroll
       for (int k = 0; k < RE_K; ++k)
@@ -436,11 +440,11 @@ __device__ __forceinline__ void row_pass_q(const ReTronArgs& a, long long r0, lo
         if (valid) {
           loss_t<LOSS>(dot[u] + rs[u][1], rs[u][2], l, dl, d2);
           if (gl == 0) {
-            fpart += rs[u][0] * l;
-            if (MODE == 1) { Dn[i] = rs[u][0] * d2; Zn[i] = dot[u]; }
+            fpart += wx(rs[u][0], l);
+            if (MODE == 1) { Dn[i] = wx(rs[u][0], d2); Zn[i] = dot[u]; }
           }
         }
-        t = rs[u][0] * dl;
+        t = wx(rs[u][0], dl);
       }
       if (qa[u] < qb[u]) {
         int k[4];
@@ -1027,8 +1031,8 @@ void re_tron_lean_kernel(ReTronArgs a) {
         double l, dl, d2;
         loss_t<LOSS>(gld(a.off + i), gld(a.y + i), l, dl, d2);
         const double wi = gld(a.wt + i);
-        s2[0] += wi * l;
-        s2[1] += (wi * dl) * (wi * dl);
+        s2[0] += wx(wi, l);
+        s2[1] += wx(wi, dl) * wx(wi, dl);
       }
       block_sums<2, LEAN_NW>(s2, red, parity);
       f0z = s2[0];
@@ -1386,10 +1390,10 @@ __global__ __launch_bounds__(64) void re_tron_tall_kernel(ReTronArgs a) {
         const long long i = r0 + b + r;
         double l, dl, d2;
         loss_t<LOSS>(s + of, yy, l, dl, d2);
-        t = wt * dl;
-        h = wt * d2;
+        t = wx(wt, dl);
+        h = wx(wt, d2);
         if (q == 0) {
-          fp += wt * l;
+          fp += wx(wt, l);
           if (mode == 1) {
             Z[nb][i] = s;
             if (!FH) D[nb][i] = h;
@@ -1634,9 +1638,9 @@ __global__ __launch_bounds__(64) void rs_tron_big_kernel(int B, int n, const dou
     for (int e = 0; e < E; ++e) {
       double l = 0.0, dl = 0.0, d2 = 0.0;
       if (on[e]) loss_t<LOSS>(z[e] + off[e], y[e], l, dl, d2);
-      fl[e] = wt[e] * l + 0.5 * l2 * v[e] * v[e];
-      t[e] = wt[e] * dl;
-      Dw[e] = wt[e] * d2;
+      fl[e] = wx(wt[e], l) + 0.5 * l2 * v[e] * v[e];
+      t[e] = wx(wt[e], dl);
+      Dw[e] = wx(wt[e], d2);
     }
     f = gsum(fl);
     mvt(t, gr);
@@ -1959,10 +1963,10 @@ __global__ __launch_bounds__(RS_THREADS) void re_tron_res_kernel(ReTronArgs a, R
               const double wt = rW[r];
               double l, dl, d2;
               loss_t<LOSS>(dot + rO[r], rY[r], l, dl, d2);
-              tt = wt * dl;
+              tt = wx(wt, dl);
               if (gl == 0) {
-                fpart += wt * l;
-                if (mode == 1) { rD[nb * CAP + r] = wt * d2; rZ[nb * CAP + r] = dot; }
+                fpart += wx(wt, l);
+                if (mode == 1) { rD[nb * CAP + r] = wx(wt, d2); rZ[nb * CAP + r] = dot; }
               }
             }
           }

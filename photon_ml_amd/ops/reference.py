@@ -19,6 +19,7 @@ import torch
 warnings.filterwarnings("ignore", message="Sparse CSR tensor support is in beta state")
 
 from ..data.matrix import LabeledData
+from ..function.losses import weighted
 
 
 def _to_torch_csr(m: sp.csr_matrix, device, dtype=torch.float64) -> torch.Tensor:
@@ -110,27 +111,27 @@ class TorchGLMData(GLMComputable):
     def value_grad_sums(self, loss, w_eff, margin_shift):
         z = self._xv(w_eff) + margin_shift + self.o
         l, dl = loss.loss_and_dz(z, self.y)
-        r = self.wt * dl
-        return float(torch.sum(self.wt * l)), float(torch.sum(r)), self._xtv(r)
+        r = weighted(self.wt, dl)
+        return float(torch.sum(weighted(self.wt, l))), float(torch.sum(r)), self._xtv(r)
 
     def zero_point_sums(self, loss, margin_shift):
         """[F, S, ||c||^2, ||X||_F^2] at w = 0 (see DeviceGLMData.zero_point_sums)."""
         l, dl = loss.loss_and_dz(self.o + margin_shift, self.y)
-        c = self.wt * dl
+        c = weighted(self.wt, dl)
         xsq = float(torch.sum(self.x.values() ** 2)) if self.n_rows else 0.0
-        return [float(torch.sum(self.wt * l)), float(torch.sum(c)), float(torch.dot(c, c)), xsq]
+        return [float(torch.sum(weighted(self.wt, l))), float(torch.sum(c)), float(torch.dot(c, c)), xsq]
 
     def hv_sums(self, loss, w_eff, margin_shift, v_eff, v_shift):
         z = self._xv(w_eff) + margin_shift + self.o
         u = self._xv(v_eff) - v_shift
         if getattr(self, "_track_u", False):
             self._u = u
-        e = self.wt * loss.dzz(z, self.y) * u
+        e = weighted(self.wt, loss.dzz(z, self.y)) * u
         return self._xtv(e), float(torch.sum(e))
 
     def hdiag_sums(self, loss, w):
         z = self._xv(w) + self.o
-        d = self.wt * loss.dzz(z, self.y)
+        d = weighted(self.wt, loss.dzz(z, self.y))
         if self.n_rows == 0:
             return torch.zeros(self.dim, dtype=torch.float64, device=self.device)
         return torch.mv(self.x2t, d)
@@ -148,14 +149,14 @@ class TorchGLMData(GLMComputable):
 
     def ls_eval(self, loss, t: float):
         l, dl = loss.loss_and_dz(self._z0 + t * self._zd, self.y)
-        return float(torch.sum(self.wt * l)), float(torch.sum(self.wt * dl * self._zd))
+        return float(torch.sum(weighted(self.wt, l))), float(torch.sum(weighted(self.wt, dl) * self._zd))
 
     def ls_finish_sums(self, loss, t: float, w_eff, shift, need_s: bool = True):
         self._track_u = False
         z = self._z0 + t * self._zd
         l, dl = loss.loss_and_dz(z, self.y)
-        r = self.wt * dl
-        return float(torch.sum(self.wt * l)), float(torch.sum(r)), self._xtv(r)
+        r = weighted(self.wt, dl)
+        return float(torch.sum(weighted(self.wt, l))), float(torch.sum(r)), self._xtv(r)
 
     # TRON trial in margin space (see DeviceGLMData.step_begin): fp64 reference
     def step_begin(self, w_eff, shift) -> bool:

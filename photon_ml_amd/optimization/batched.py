@@ -22,6 +22,7 @@ from typing import Optional
 
 import torch
 
+from ..function.losses import weighted
 from .optimizer import ConvergenceReason
 
 REASON_CODES = {0: None, 1: ConvergenceReason.MAX_ITERATIONS, 2: ConvergenceReason.OBJECTIVE_NOT_IMPROVING,
@@ -86,8 +87,8 @@ class BatchedGLMData:
     def value_grad(self, loss, W, l2: float):
         z = self.margins(W)
         l, dl = loss.loss_and_dz(z, self.y)
-        f = (self.w * l).sum(1)
-        g = self._mv(self.w * dl, trans=True)
+        f = weighted(self.w, l).sum(1)
+        g = self._mv(weighted(self.w, dl), trans=True)
         if l2 > 0:
             f = f + 0.5 * l2 * (W * W).sum(1)
             g = g + l2 * W
@@ -99,7 +100,7 @@ class BatchedGLMData:
         key = self._dzz_key
         if key is not None and key[0] is W and key[1] == W._version and key[2] is loss:
             return self._dzz
-        self._dzz = self.w * loss.dzz(self.margins(W), self.y)
+        self._dzz = weighted(self.w, loss.dzz(self.margins(W), self.y))
         self._dzz_key = (W, W._version, loss)
         return self._dzz
 
@@ -113,7 +114,7 @@ class BatchedGLMData:
         return h + l2 * V if l2 > 0 else h
 
     def hdiag(self, loss, W, l2: float):
-        D = self.w * loss.dzz(self.margins(W), self.y)
+        D = weighted(self.w, loss.dzz(self.margins(W), self.y))
         h = torch.bmm((self.X * self.X).transpose(1, 2), D.unsqueeze(-1)).squeeze(-1)
         return h + l2 if l2 > 0 else h
 
@@ -197,8 +198,8 @@ class SegmentedGLMData:
     def value_grad(self, loss, W, l2: float, active=None):
         z = self.margins(W, active)
         l, dl = loss.loss_and_dz(z, self.y)
-        f = self._rowsum(self.w * l)
-        g = self.glm.rmatvec(self.w * dl)
+        f = self._rowsum(weighted(self.w, l))
+        g = self.glm.rmatvec(weighted(self.w, dl))
         if l2 > 0:
             f = f + 0.5 * l2 * self.bdot(W, W)
             g = g + l2 * W
@@ -214,7 +215,7 @@ class SegmentedGLMData:
         if (key is not None and key[0] is W and key[1] == W._version and key[2] is loss
                 and (key[3] is None or mk is not None)):
             return self._dzz
-        self._dzz = self.w * loss.dzz(self.glm.matvec(W) + self.o, self.y)
+        self._dzz = weighted(self.w, loss.dzz(self.glm.matvec(W) + self.o, self.y))
         self._dzz_key = (W, W._version, loss, None if mk is None else True)
         return self._dzz
 
@@ -225,7 +226,7 @@ class SegmentedGLMData:
         return h + l2 * V if l2 > 0 else h
 
     def hdiag(self, loss, W, l2: float):
-        D = self.w * loss.dzz(self.margins(W), self.y)
+        D = weighted(self.w, loss.dzz(self.margins(W), self.y))
         h = self.glm.rmatvec(D, square=True)
         return h + l2 if l2 > 0 else h
 

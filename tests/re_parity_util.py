@@ -175,3 +175,85 @@ def gpu_fit(data, loss, l2, tol, max_iter, monkeypatch, partial=None, start=None
     its = {ids[k]: int(got["it"][i]) for i, k in enumerate(order)}
     reasons = {ids[k]: REASON_CODES[int(got["rc"][i])] for i, k in enumerate(order)}
     return W, its, reasons, c, m
+
+
+# The shapes and routes of the fused random-effect solvers (test_re_weighted_parity_gpu.py describes each route).
+SHAPES = {
+    # name: (sizes, d_pool, nnz_row, dense_pool, seed)
+    "rs": ([20] * 3 + [17] * 2 + [32] * 2 + [25] + [48] * 2 + [41] + [64] * 2 + [57], 120, 12, False, 2),
+    "rs_big": ([80] * 2 + [100] * 2 + [128] * 2, 150, 0, True, 3),
+    "lean": ([90, 120, 150, 75] * 2, 300, 16, False, 9),
+    "lean_scalar": ([90, 120, 150, 75] * 2, 300, 6, False, 14),
+    "tall": ([150, 90, 200, 65] * 2, 40, 0, True, 7),
+    "csr": ([90, 110] * 2, 1800, 24, False, 3),
+    "dense_wide": ([80, 95, 70] * 2, 100, 0, True, 4),
+    "dense_hess": ([80, 95] * 2, 30, 0, True, 10),
+}
+ROUTES = {
+    # name: (shape, environment, RESIDENT policy, layout)
+    "rs": ("rs", {}, "0", "segmented"),
+    "rs_big": ("rs_big", {}, "0", "segmented"),
+    "lean_quad": ("lean", {"PML_RE_ROW_SPACE": "0"}, "0", "segmented"),
+    "lean_scalar": ("lean_scalar", {"PML_RE_ROW_SPACE": "0"}, "0", "segmented"),
+    "resident": ("lean", {"PML_RE_ROW_SPACE": "0"}, "force", "segmented"),
+    "tall": ("tall", {}, "0", "segmented"),
+    "csr": ("csr", {"PML_RE_ROW_SPACE": "0"}, "0", "segmented"),
+    "dense_wide": ("dense_wide", {}, "0", "dense"),
+    "dense_hess": ("dense_hess", {}, "0", "dense"),
+    "pass": ("lean", {"PML_RE_FUSED": "0", "PML_RE_ROW_SPACE": "0"}, "0", "segmented"),
+}
+
+
+def _set_route(route, monkeypatch):
+    import photon_ml_amd.optimization.entity_tron as et
+    shape, env, resident, layout = ROUTES[route]
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    monkeypatch.setattr(et, "RESIDENT", resident)
+    return shape, layout
+
+
+def _check_routing(route, c, data):
+    """The case reached the kernel it is named after (a case that routes elsewhere fails)."""
+    if route in ("dense_wide", "dense_hess"):
+        assert c.dataset.layout == "dense" and len(c.dataset.buckets)
+        fz = [c._dense_fused(b, bk, 0.0) for b, bk in enumerate(c.dataset.buckets)]
+        assert all(f is not None for f in fz)
+        if route == "dense_wide":
+            assert all(f.quad and f.d > 64 for f in fz)
+        else:
+            assert all(f.d <= 64 and f.launch[2] for f in fz)
+        return
+    assert c.dataset.layout == "segmented"
+    if route == "pass":
+        # the fused solvers are off: no components at all, the block-diagonal passes under batched_tron
+        assert getattr(c, "_comps", None) is None and getattr(c, "_rs", None) is None
+        return
+    rs, fused, sub = c._comps
+    assert sub is None
+    if route in ("rs", "rs_big"):
+        assert fused is None and rs is not None and rs.B == len(c.dataset.entity_ids)
+        ns = {cl.n for cl in rs.classes}
+        if route == "rs":
+            assert ns >= {20, 32, 48, 64} and max(ns) <= 64, ns
+        else:
+            assert max(ns) > 64, ns
+        return
+    assert rs is None and fused is not None and fused.B == len(c.dataset.entity_ids)
+    if route == "resident":
+        assert fused.res is not None and fused.res["n"] > 0
+        return
+    assert fused.res is None and fused.launches
+    if route == "lean_quad":
+        assert fused.quad and all(not h and dm <= 1024 for dm, _, h in fused.launches)
+    elif route == "lean_scalar":
+        assert not fused.quad and all(not h and dm <= 1024 for dm, _, h in fused.launches)
+    elif route == "tall":
+        assert all(h for _, _, h in fused.launches)
+    elif route == "csr":
+        x, ids = data.shards["user"].tocsr(), data.id_tags["userId"]
+        d_e = [len(np.unique(x[ids == e].indices)) for e in np.unique(ids)]
+        assert all(1024 < d <= 2048 for d in d_e), d_e
+        assert all(dm > 1024 and not h for dm, _, h in fused.launches)
+    else:
+        raise AssertionError(route)
