@@ -137,7 +137,7 @@ def generate_device_shard(n_rows: int, n_features: int, nnz_per_row: int, device
                           task=TaskType.LOGISTIC_REGRESSION, rank: int = 0, progress=None, layout: str = "auto"):
     """Generate a :class:`DeviceGLMData` directly in device memory (see module docstring)."""
     from ..ops.device import DeviceGLMData, SegChunk, VAL_DTYPE, resolve_layout
-    from ..ops.tiled import TLFwdChunk, TLTChunk, shard_tall
+    from ..ops.tiled import TLFwdChunk, TLTChunk, shard_tall, shard_tgroup
 
     dev = torch.device(device)
     prec = {"bf16": 0, "f32": 1, "f64": 2}[precision]
@@ -199,7 +199,8 @@ def generate_device_shard(n_rows: int, n_features: int, nnz_per_row: int, device
             col = idx.to(torch.int64)
             del idx
             csr.append(TLFwdChunk(rp, col, val, n_features, tall=shard_tall(n_features, min(chunk_rows, n_rows))))
-            csc.append(TLTChunk(rp, col, val, n_features, chunk_rows, cbits=cbits, item_entries=item_entries))
+            csc.append(TLTChunk(rp, col, val, n_features, chunk_rows, cbits=cbits, item_entries=item_entries,
+                                tgroup=shard_tgroup(n_features, n_rows, chunk_rows)))
             raw[ci] = None
             del col, val, rp
             if progress is not None:

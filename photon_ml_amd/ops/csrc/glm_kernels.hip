@@ -621,6 +621,10 @@ __global__ __launch_bounds__(NTHREADS) void reduce_stats_l1_kernel(const double*
 //              reads the columns of four times as many rows and touches fewer distinct lines.
 //   transpose: COLUMN TILES of 2^cbits columns; inside a tile entries are sorted by (row, column) and packed as
 //              (local_row << cbits) | (col & (2^cbits-1)). Gathers x[row] walk the per-row vector in order.
+//              TILE GROUPS (big bf16 / fp32 shards; tl_t_group): four consecutive single-item tiles as one unit.
+//              Narrow rounds stay per tile; the tiles' wide entries are FOUR sub-windows (one per wave quarter of
+//              tl_t_item) sorted by (row, column in group) and packed (local_row << 12) | col12, so a wide gather
+//              reads the per-row values of four tiles' entries; same additions in the same order: same bits.
 // Determinism: each wave owns a private LDS accumulator row and walks its entries in a fixed order, and the 4
 // wave rows are summed in a fixed order (tall forward units: ONE row per work-group whose slots are added to by one
 // wave at a time -- disjoint slot ranges per wave, then a single wave after a barrier); items of a column tile that is split across work-groups write fp64
@@ -1379,6 +1383,111 @@ __global__ __launch_bounds__(NW * 64) void tl_t_multi_kernel(const int* __restri
                                             (const VT*)pc[1], nar, x + q[5], G, dim, parts, acc);
 }
 
+// TILE GROUPS (ops/tiled.py, "tile groups"): four consecutive single-item tiles 4g .. 4g+3 of one chunk as one unit.
+// The narrow rounds stay per tile (16-bit packs, 10 slot bits); the tiles' wide entries are merged into FOUR
+// sub-windows q = 0..3, sub-window q holding what wave q of tl_t_item walks of each tile (the tile's wide rounds
+// [nr q / 4, nr (q + 1) / 4)), sorted by (row, column in group) and packed (local_row << 12) | col12 -- a wide
+// gather then reads the per-row values of four tiles' entries and touches fewer distinct lines. One work-group of
+// 4 waves and ONE accumulator row acc[4096] (32 KB), and the running total of a thread's 16 slots in registers.
+// For q = 0..3: wave k walks quarter q of tile k's narrow rounds ([n_lo + nn q / 4, n_lo + nn (q + 1) / 4)) into
+// acc + 1024 k; barrier; one wave walks sub-window q; barrier; tot = q ? tot + acc : acc, acc = 0; barrier.
+// Per column these are the additions of tl_t_item<.., NW = 4> with fp64 accumulators, in its order and grouping:
+// accumulator q = narrow quarter q, then wide quarter q, each in (row) order from +0.0, and ((A0 + A1) + A2) + A3.
+// Group row, 24 ints: {tile0, part[4], n_lo[4], n_hi[4], e_lo[4], e_hi[4], chunk, row_base, (host use)}; part k: -1 = add
+// into G, >= 0 = partial row, TL_TG_EMPTY = tile k has no entries in this chunk (nothing is written, as no item
+// of tl_t_item would exist).
+#define TL_TG_BITS 12
+#define TL_TG_SUB 10
+#define TL_TG_COLS 24
+#define TL_TG_EMPTY (-2)
+template <typename VT, typename XT, bool SQ, int PT>
+__device__ __forceinline__ void tl_t_group(const int* __restrict__ q, const uint32_t* __restrict__ pack,
+                                           const VT* __restrict__ val, const TLNarrow& nar,
+                                           const XT* __restrict__ x, double* __restrict__ G, int dim,
+                                           double* __restrict__ parts, double* acc) {
+  constexpr int NW = 4, C = 1 << TL_TG_SUB, NS = (1 << TL_TG_BITS) / (NW * 64);
+  for (int i = threadIdx.x; i < (1 << TL_TG_BITS); i += NW * 64) acc[i] = 0.0;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int n_lo = q[5 + w], nn = q[9 + w] - n_lo;          // scalar loads: this wave's tile
+  double tot[NS];
+  __syncthreads();
+#pragma unroll 1
+  for (int k = 0; k < 4; ++k) {
+    const int a = n_lo + (nn * k) / 4, b = n_lo + (nn * (k + 1)) / 4;
+    if (b > a) tl_narrow<VT, XT, double, SQ, 1, (PT >= 5 ? 4 : 2)>(nar, a, b, TL_TG_SUB, x, acc + (w << TL_TG_SUB));
+    __syncthreads();
+    const int e_lo = q[13 + k], e_hi = q[17 + k];
+    if (w == k && e_hi > e_lo) {                             // (a different wave per quarter: any one will do)
+      if (PT == 6) tl_stream_ring<VT, XT, double, SQ, 1, 5, 2>(pack, val, x, e_lo, e_hi, TL_TG_BITS, acc, nullptr);
+      else if (PT == 5) tl_stream_ring<VT, XT, double, SQ, 1, 3, 1>(pack, val, x, e_lo, e_hi, TL_TG_BITS, acc, nullptr);
+      else tl_stream_ring<VT, XT, double, SQ, 1, 2, 0>(pack, val, x, e_lo, e_hi, TL_TG_BITS, acc, nullptr);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+      const int i = threadIdx.x + j * NW * 64;
+      tot[j] = k == 0 ? acc[i] : tot[j] + acc[i];
+      acc[i] = 0.0;
+    }
+    __syncthreads();
+  }
+#pragma unroll
+  for (int j = 0; j < NS; ++j) {
+    const int i = threadIdx.x + j * NW * 64, t = i >> TL_TG_SUB, c = i & (C - 1);   // t = j / 4: compile-time
+    const int part = q[1 + t];
+    if (part >= 0) parts[(size_t)part * C + c] = tot[j];
+    else if (part == -1) {
+      const int col = ((q[0] + t) << TL_TG_SUB) + c;
+      if (col < dim) G[col] += tot[j];
+    }
+  }
+}
+
+template <typename VT, typename XT, bool SQ, int PT>
+__global__ __launch_bounds__(256, 5) void tl_tg_kernel(const int* __restrict__ groups,
+                                                     const uint32_t* __restrict__ pack, const VT* __restrict__ val,
+                                                     TLNarrow nar, const XT* __restrict__ x, double* __restrict__ G,
+                                                     int dim, double* __restrict__ parts,
+                                                     const unsigned char* __restrict__ live) {
+  __shared__ double acc[1 << TL_TG_BITS];     // exactly 32 KB, nothing else in LDS
+  if (live && !live[blockIdx.x]) return;
+  tl_t_group<VT, XT, SQ, PT>(groups + TL_TG_COLS * blockIdx.x, pack, val, nar, x, G, dim, parts, acc);
+}
+
+// Shard-wide: the groups AND the items of every chunk in ONE launch -- blocks [0, ngroups) run the groups (the long
+// units first), the others the items exactly as tl_t_multi_kernel<VT, XT, double, SQ, 1024, 2, 4, 3> does (tl_t_item on
+// the same 32 KB viewed as 4 wave rows). Measured against a launch of its own for the groups: the items fill the CUs
+// that the last long groups leave idle (headline 33.3-33.6 vs 34.3 ms/step, profiles/tl_t_groups.md). Stream pointers
+// as in tl_fwd_multi_kernel, gated like tl_t_multi_kernel; live / live_g: optional flags per item / per group.
+template <typename VT, typename XT, bool SQ, int PT>
+__global__ __launch_bounds__(256, 5) void tl_tg_multi_kernel(const int* __restrict__ groups, int ngroups,
+                                                              const int* __restrict__ items,
+                                                              const unsigned long long* __restrict__ ptrs,
+                                                              const XT* __restrict__ x, double* __restrict__ G, int dim,
+                                                              double* __restrict__ parts,
+                                                              const unsigned char* __restrict__ live,
+                                                              const unsigned char* __restrict__ live_g,
+                                                              const int* __restrict__ gate) {
+  __shared__ double acc[1 << TL_TG_BITS];     // exactly 32 KB, nothing else in LDS
+  if (gate && *gate == 0) return;
+  const int b = __builtin_amdgcn_readfirstlane(blockIdx.x);
+  if (b < ngroups) {
+    if (live_g && !live_g[b]) return;
+    const int* q = groups + TL_TG_COLS * b;
+    const unsigned long long* pc = ptrs + 6 * q[21];
+    const TLNarrow nar = {(const uint16_t*)pc[2], (const void*)pc[3], (const int*)pc[4], nullptr};
+    tl_t_group<VT, XT, SQ, PT>(q, (const uint32_t*)pc[0], (const VT*)pc[1], nar, x + q[22], G, dim, parts, acc);
+  } else {
+    if (live && !live[b - ngroups]) return;
+    const int* q = items + 8 * (b - ngroups);
+    const unsigned long long* pc = ptrs + 6 * q[0];
+    const TLNarrow nar = {(const uint16_t*)pc[2], (const void*)pc[3], (const int*)pc[4], (const int*)pc[5]};
+    tl_t_item<VT, XT, double, SQ, 1 << TL_TG_SUB, 2, 4, 3>(q[1], q[2], q[3], q[4], q[6], q[7], TL_TG_SUB,
+                                                         (const uint32_t*)pc[0], (const VT*)pc[1], nar, x + q[5], G,
+                                                         dim, parts, (double(*)[1 << TL_TG_SUB])acc);
+  }
+}
+
 // Combine the partial rows of split tiles, deterministically, in two levels (a hot tile can have hundreds of
 // items: one work-group per tile would serialise its whole partial block):
 //   level 1: unit u sums parts [cu[3u+1], cu[3u+2]) (<= TL_SEG consecutive items of one tile) -> l1[u * C + c]
@@ -1459,6 +1568,8 @@ struct TLTDesc {
   TLNarrow nar;
   const unsigned char* live;      // optional per-item flags (0 = skip) and per-split-tile flags for the combine
   const unsigned char* live_mt;
+  const int* groups; int ngroups; // tile groups (tl_tg_kernel; 24 ints each) and their optional live flags
+  const unsigned char* live_g;
 };
 // Shard-wide transpose: items of every chunk (8 ints, see tl_t_multi_kernel) with per-chunk stream pointers.
 struct TLTMultiDesc {
@@ -1467,6 +1578,8 @@ struct TLTMultiDesc {
   const int* cu; int ncu; int nparts_total; int il;
   const unsigned char* live;
   const unsigned char* live_mt;
+  const int* groups; int ngroups; // tile groups of every chunk (tl_tg_multi_kernel) and their optional live flags
+  const unsigned char* live_g;
 };
 
 // Runtime TL configuration (pml_tl_config; read by the experiment build's launch ladder only, see TL_EXPERIMENT):
@@ -1667,8 +1780,36 @@ static int tl_t_combine(const Desc* c, double* G, double* parts, hipStream_t st)
   return 0;
 }
 
+// Tile groups: f(integral_constant<int, PT>) with the ring pipeline of the wide phase, as tl_with_tall. -22: a
+// descriptor the group kernels cannot run (fp64 data, plain order, tiles of another width).
+#define TL_TG_P 3     // the ring of the wide phase: 3 (S2/D0) measured faster than 6 (S5/D2), which spills at 96 VGPRs
+template <typename XT, typename F>
+static int tl_with_tg(int cbits, int il, F f) {
+  if constexpr (sizeof(XT) == 8) {
+    return -22;
+  } else {
+    if (cbits != TL_TG_SUB || !il) return -22;
+    if constexpr (TL_EXPERIMENT) {
+      if (g_tl_deep_t == 2) f(std::integral_constant<int, 6>{});
+      else if (g_tl_deep_t) f(std::integral_constant<int, 5>{});
+      else f(std::integral_constant<int, 3>{});
+    } else {
+      f(std::integral_constant<int, TL_TG_P>{});
+    }
+    return 0;
+  }
+}
+
 template <typename VT, typename XT, bool SQ>
 static int tl_t_impl(const TLTDesc* c, const void* x, double* G, double* parts, hipStream_t st) {
+  if (c->ngroups > 0) {      // the groups first: the longest units of a chunk
+    const int rt = tl_with_tg<XT>(c->cbits, c->il, [&](auto pt) {
+      hipLaunchKernelGGL((tl_tg_kernel<VT, XT, SQ, decltype(pt)::value>), dim3(c->ngroups), dim3(256), 0, st,
+                         c->groups, c->pack, (const VT*)c->val, c->nar, (const XT*)x, G, c->dim, parts, c->live_g);
+    });
+    if (rt) return rt;
+    LAUNCH_CHECK();
+  }
   if (c->nitems <= 0) return 0;
   const int rc = tl_with_acc<XT>(c->cbits, [&](auto acc) {
     tl_with_pipe<4, 1>(c->il, g_tl_waves_t, g_tl_deep_t, g_tl_pipe_t, [&](auto pipe) {
@@ -1685,6 +1826,16 @@ static int tl_t_impl(const TLTDesc* c, const void* x, double* G, double* parts, 
 
 template <typename VT, typename XT, bool SQ>
 static int tl_t_multi_impl(const TLTMultiDesc* c, const void* x, double* G, double* parts, hipStream_t st) {
+  if (c->ngroups > 0) {      // groups and items in one launch (tl_tg_multi_kernel)
+    const int rt = tl_with_tg<XT>(c->cbits, c->il, [&](auto pt) {
+      hipLaunchKernelGGL((tl_tg_multi_kernel<VT, XT, SQ, decltype(pt)::value>), dim3(c->ngroups + (c->nitems > 0 ? c->nitems : 0)),
+                         dim3(256), 0, st, c->groups, c->ngroups, c->items, c->ptrs, (const XT*)x, G, c->dim, parts,
+                         c->live, c->live_g, g_gate);
+    });
+    if (rt) return rt;
+    LAUNCH_CHECK();
+    return tl_t_combine(c, G, parts, st);
+  }
   if (c->nitems <= 0) return 0;
   const int rc = tl_with_acc<XT>(c->cbits, [&](auto acc) {
     tl_with_pipe<4, 2>(c->il, g_tl_waves_t, g_tl_deep_t, g_tl_pipe_t, [&](auto pipe) {
@@ -1863,6 +2014,7 @@ template <typename VT>
 static int tl_colstats_impl(const TLTDesc* c, double* const* sums, double* mx, double* mn, double* parts,
                             hipStream_t st) {
   if (c->cbits < 1 || c->cbits > (sizeof(VT) == 8 ? 11 : TL_MAXBITS)) return -22;
+  if (c->ngroups > 0) return -22;     // these readers walk items only: pass the chunk's ungrouped copy (ops/tiled.py)
   if (c->nitems <= 0) return 0;
   for (int which = 0; which < 4; ++which) {
     auto launch = [&](auto maxr, auto nw) {

@@ -28,7 +28,7 @@ import torch
 from ..data.matrix import LabeledData
 from .native import SegChunkDesc, check, require_glm_lib, stream_handle
 from .reference import GLMComputable
-from .tiled import DEFAULT_ITEM_ENTRIES, TLFwdChunk, TLTChunk, shard_tall, tl_supported
+from .tiled import DEFAULT_ITEM_ENTRIES, TLFwdChunk, TLTChunk, shard_tall, shard_tgroup, tl_supported
 from ..utils.timing import phase, trace_range
 
 # Set after a tiled build's host -> device upload: GameData.prefetch_shard's copy waits for it, so the two copies do
@@ -252,14 +252,31 @@ class DeviceGLMData(GLMComputable):
                     raise ValueError(f"chunk {c}: transpose item window outside the stream")
                 if int(it[:, 3].max()) >= max(t.nparts, 1) and t.nparts:
                     raise ValueError(f"chunk {c}: transpose partial-row slot out of range")
-                self._validate_narrow(c, t, it, m, "transpose")
+                self._validate_narrow(c, t, t.narrow_table().cpu(), m, "transpose")
                 tp, _ = t.logical()
                 q = tp.cpu().to(torch.int64) & 0xFFFFFFFF
                 if q.numel() and int((q >> t.cbits).max()) >= m:
                     raise ValueError(f"chunk {c}: transpose gather row >= chunk rows")
-                cols = (torch.repeat_interleave(it[:, 0], t.unit_counts().cpu()) << t.cbits) + (q & ((1 << t.cbits) - 1))
+                cols = ((torch.repeat_interleave(t.unit_tiles().cpu(), t.unit_counts().cpu()) << t.cbits)
+                        + (q & ((1 << t.cbits) - 1)))
                 if q.numel() and int(cols.max()) >= t.dim:
                     raise ValueError(f"chunk {c}: transpose column >= dim")
+            if getattr(t, "ngroups", 0):
+                g = t.groups.cpu().to(torch.int64)
+                if (int(g[:, 13:17].min()) < 0 or bool((g[:, 13:17] % 256 != 0).any())
+                        or int(((g[:, 17:21] + 255) // 256 * 256).max()) > t.pack.numel()
+                        or bool((g[:, 17:21] < g[:, 13:17]).any())):
+                    raise ValueError(f"chunk {c}: tile-group window outside the stream")
+                if int(g[:, 5:9].min()) < 0 or int(g[:, 9:13].max()) > t.nbase.numel() or bool(
+                        (g[:, 9:13] < g[:, 5:9]).any()):
+                    raise ValueError(f"chunk {c}: tile-group narrow rounds out of range")
+                if int(g[:, 0].min()) < 0 or ((int(g[:, 0].max()) + 4) << t.cbits) > ((t.dim + 1023) >> 10 << 10):
+                    raise ValueError(f"chunk {c}: tile group outside the column window")
+                if not t.nitems:
+                    self._validate_narrow(c, t, t.narrow_table().cpu(), m, "transpose")
+                    gp, _ = t.logical()
+                    if gp.numel() and int(((gp.cpu().to(torch.int64) & 0xFFFFFFFF) >> t.cbits).max()) >= m:
+                        raise ValueError(f"chunk {c}: transpose gather row >= chunk rows")
         if self.parts.numel() < max([c.parts_needed for c in self.csr + self.csc] + [1]):
             raise ValueError("partial-row scratch too small")
         self._validate_multi()
@@ -286,6 +303,14 @@ class DeviceGLMData(GLMComputable):
                 if ch.il and r.shape[0] and (int(r[:, 2].min()) < 0 or int((r[:, 2] + (r[:, 3] - r[:, 2] + 255) // 256 * 256).max())
                                    > ch.pack.numel() or int(r[:, 7].max()) > ch.nbase.numel() * (ch.n_narrow_rounds > 0)):
                     raise ValueError(f"chunk {c}: shard-wide transpose table outside the chunk's streams")
+            g = mt.groups.cpu().to(torch.int64)
+            for c, ch in enumerate(self.csc):
+                r = g[g[:, 21] == c]
+                if r.shape[0] and (int(r[:, 13:17].min()) < 0 or int(((r[:, 17:21] + 255) // 256 * 256).max()) > ch.pack.numel()
+                                   or int(r[:, 9:13].max()) > ch.nbase.numel() * (ch.n_narrow_rounds > 0)
+                                   or int(r[:, 1:5].max()) >= max(mt.nparts, 1)
+                                   or int(r[:, 22].min()) != self.row_starts[c] or int(r[:, 22].max()) != self.row_starts[c]):
+                    raise ValueError(f"chunk {c}: shard-wide tile-group table outside the chunk's streams")
 
     @staticmethod
     def _validate_narrow(c: int, ch, table: torch.Tensor, xlen: int, what: str):
@@ -377,7 +402,8 @@ class DeviceGLMData(GLMComputable):
                 col = torch.from_numpy(xc.indices.astype(np.int64)).to(dev)
                 val = torch.from_numpy(xc.data.astype(np.float64)).to(dev).to(vdt)
                 csr.append(TLFwdChunk(rp, col, val, dc, tall=shard_tall(dmax, min(chunk_rows, n))))
-                csc.append(TLTChunk(rp, col, val, dc, chunk_rows, cbits=cbits, item_entries=item_entries))
+                csc.append(TLTChunk(rp, col, val, dc, chunk_rows, cbits=cbits, item_entries=item_entries,
+                                    tgroup=shard_tgroup(dmax, n, chunk_rows)))
                 continue
             sp_ = (xc.indptr - xc.indptr[0]).astype(np.int32)
             csr.append(SegChunk(sp_, torch.from_numpy(xc.indices.astype(np.int32)),
@@ -439,10 +465,11 @@ class DeviceGLMData(GLMComputable):
     def from_device_csr(indptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, y, offsets, weights, dim: int,
                         device="cuda", precision: str = "f64", chunk_rows: int = 1 << 20,
                         item_entries: Optional[int] = None, col_windows: bool = False,
-                        tall: Optional[bool] = None):
+                        tall: Optional[bool] = None, tgroup: Optional[bool] = None):
         """Tiled-layout shard built from device-resident CSR arrays: chunking, column windows, the forward
         block sort and the transpose tile sort all run on the device (no host round trip of the non-zeros).
-        ``tall``: force the forward copies' tall units on / off (``tiled.TLFwdChunk``; None: the shard rule)."""
+        ``tall``: force the forward copies' tall units on / off (``tiled.TLFwdChunk``; None: the shard rule);
+        ``tgroup``: the same for the transpose copies' tile groups (``tiled.TLTChunk``; None: ``tiled.shard_tgroup``)."""
         dev = torch.device(device)
         vdt = VAL_DTYPE[PRECISIONS[precision]]
         indptr = indptr.to(dev, torch.int64)
@@ -478,7 +505,8 @@ class DeviceGLMData(GLMComputable):
             v = val[ea:eb].to(dev).to(vdt)
             csr.append(TLFwdChunk(rp, c, v, hi - lo,
                                   tall=shard_tall(dmax, min(chunk_rows, n)) if tall is None else tall))
-            csc.append(TLTChunk(rp, c, v, hi - lo, chunk_rows, cbits=cbits, item_entries=item_entries))
+            csc.append(TLTChunk(rp, c, v, hi - lo, chunk_rows, cbits=cbits, item_entries=item_entries,
+                                tgroup=shard_tgroup(dmax, n, chunk_rows) if tgroup is None else tgroup))
             col_lo.append(lo)
             del c, v
         chunk_phase.__exit__(None, None, None)
@@ -517,11 +545,23 @@ class DeviceGLMData(GLMComputable):
         # few rows kept: filter the narrow rounds too (all-wide copy); else share them (see RowCompaction)
         frac = float(keep[:n].sum()) / max(n, 1)
         filt = frac < NARROW_FILTER_BELOW
+        # transpose copies with tile groups: the copy is made of their ungrouped twins (built once per shard), whose
+        # results are the grouped shard's bit for bit; the sampled rounds would not keep the groups' quarters
+        csc, multi_t, grouped = self.csc, self._multi_t, any(getattr(ch, "ngroups", 0) for ch in self.csc)
+        if grouped:
+            if getattr(self, "_csc_plain", None) is None:
+                from .tiled import TLTMulti
+                plain = [ch.ungrouped() for ch in self.csc]
+                C = 1 << plain[0].cbits
+                self._csc_plain = (plain, None if self._multi_t is None else TLTMulti(
+                    plain, self.row_starts, self.dim,
+                    tile_offsets=[lo // C for lo in self.col_lo] if any(self.col_lo) else None))
+            csc, multi_t = self._csc_plain
         jobs = []
         for c in range(len(self.csr)):
             kc = keep[self.row_starts[c]: self.row_starts[c + 1]]
             jobs.append(RowCompaction(self.csr[c], kc, True, filt))
-            jobs.append(RowCompaction(self.csc[c], kc, False, filt))
+            jobs.append(RowCompaction(csc[c], kc, False, filt))
         sizes = torch.stack([torch.stack([j.total, j.kept]) for j in jobs]).tolist()    # one host sync
         out = [j.finish(int(t), int(k)) for j, (t, k) in zip(jobs, sizes)]
         view = DeviceGLMData(out[0::2], out[1::2], self.row_starts, self.y, self.o, self.wt, self.dim,
@@ -551,9 +591,9 @@ class DeviceGLMData(GLMComputable):
             view._multi_ptrs = stream_ptr_table(view.csr, self.device)
             view._multi = TLFwdMultiDesc(nb.data_ptr(), nb.shape[0], self._multi.rbits, view._multi_ptrs.data_ptr(),
                                          self._multi.il, tbits=self._multi.tbits)
-        view._multi_t = None if self._multi_t is None else self._multi_t.restreamed(view.csc)
+        view._multi_t = None if multi_t is None else multi_t.restreamed(view.csc)
         gb = getattr(self, "_gbuckets", None)
-        if gb is not None and gb[1] is not None:
+        if gb is not None and gb[1] is not None and not grouped:      # (else the copy builds its own buckets)
             view._gbuckets = (gb[0], [(mt.restreamed(view.csc), c0, c1) for mt, c0, c1 in gb[1]])
         # same unit tables -> the same partial-row scratch (used in stream order); assigned last, after every
         # table this shard built above could have grown it
@@ -1067,7 +1107,12 @@ class DeviceGLMData(GLMComputable):
             for t in (ch.items[: ch.nitems, 0].to(torch.int64), ch.mt_tiles[: ch.nmt].to(torch.int64)):
                 firsts.append(col_entity[(self.col_lo[c] + t * C).clamp(0, nc - 1)])
                 lasts.append(col_entity[torch.clamp(self.col_lo[c] + (t + 1) * C - 1, max=hi).clamp(0, nc - 1)])
-            i_off.append(i_off[-1] + int(ch.nitems) + int(ch.nmt))
+            ng = int(getattr(ch, "ngroups", 0))
+            if ng:                    # tile groups: the flags follow the chunk's split tiles; 4 tiles wide each
+                t = ch.groups[:, 0].to(torch.int64)
+                firsts.append(col_entity[(self.col_lo[c] + t * C).clamp(0, nc - 1)])
+                lasts.append(col_entity[torch.clamp(self.col_lo[c] + (t + 4) * C - 1, max=hi).clamp(0, nc - 1)])
+            i_off.append(i_off[-1] + int(ch.nitems) + int(ch.nmt) + ng)
             m_off.append(i_off[-2] + int(ch.nitems))          # start of this chunk's split tiles
         t0, t1 = torch.cat(firsts), torch.cat(lasts)
         self._mgeo = (f0, f1, f_off, t0, t1, i_off, m_off)
@@ -1100,6 +1145,7 @@ class DeviceGLMData(GLMComputable):
             d = dup(ch.desc)
             d.live = live_t.data_ptr() + i_off[c]
             d.live_mt = live_t.data_ptr() + m_off[c + 1]
+            d.live_g = live_t.data_ptr() + m_off[c + 1] + int(ch.nmt)
             tdescs.append(d)
         self._masked = (fdesc, tdescs, keep)
         if MASK_STATS is not None:
@@ -1125,8 +1171,18 @@ class DeviceGLMData(GLMComputable):
         for ch in self.csc:
             it = ch.items[: ch.nitems].cpu().numpy().astype(np.int64)
             np.add.at(work, it[:, 0], it[:, 2] - it[:, 1])
+            if getattr(ch, "ngroups", 0):
+                g = ch.groups.cpu().numpy().astype(np.int64)
+                np.add.at(work, g[:, 0], (g[:, 17:21] - g[:, 13:17]).sum(1))
         cum = np.cumsum(work)
         cuts = [0] + [int(np.searchsorted(cum, cum[-1] * k / nb, side="right")) for k in range(1, nb)] + [ntiles]
+        if any(getattr(ch, "ngroups", 0) for ch in self.csc):
+            # a tile group is one unit of work: cuts on multiples of 4 global tiles (column windows that do not
+            # start on one: no buckets)
+            if any((lo // C) % 4 for lo in self.col_lo):
+                self._gbuckets = (nb, None)
+                return None
+            cuts = [c if c == ntiles else c - c % 4 for c in cuts]
         cuts = sorted(set(min(max(c, 0), ntiles) for c in cuts))
         out = []
         for t0, t1 in zip(cuts[:-1], cuts[1:]):
@@ -1414,7 +1470,8 @@ class DeviceGLMData(GLMComputable):
                 torch.full((self.dim,), float("-inf"), dtype=torch.float64, device=self.device),
                 torch.full((self.dim,), float("inf"), dtype=torch.float64, device=self.device)]
         for c, ch in enumerate(self.csc):
-            tl_colstats(self.prec, ch, self.col_lo[c], outs, self.parts)
+            # (the statistics kernels walk items: a chunk with tile groups passes its ungrouped twin, the same entries)
+            tl_colstats(self.prec, ch.ungrouped(cache=False), self.col_lo[c], outs, self.parts)
         return tuple(self._unperm(t) for t in outs)
 
     def margins(self, w, margin_shift: float = 0.0, with_offsets: bool = False):

@@ -58,7 +58,8 @@ class TLFwdMultiDesc(ctypes.Structure):
 class TLTMultiDesc(ctypes.Structure):
     _fields_ = [("items", c_void_p), ("nitems", c_int), ("cbits", c_int), ("ptrs", c_void_p),
                 ("mt_tiles", c_void_p), ("mt_ptr", c_void_p), ("nmt", c_int), ("dim", c_int), ("cu", c_void_p),
-                ("ncu", c_int), ("nparts_total", c_int), ("il", c_int), ("live", c_void_p), ("live_mt", c_void_p)]
+                ("ncu", c_int), ("nparts_total", c_int), ("il", c_int), ("live", c_void_p), ("live_mt", c_void_p),
+                ("groups", c_void_p), ("ngroups", c_int), ("live_g", c_void_p)]
 
 
 class CmpArgs(ctypes.Structure):
@@ -90,6 +91,7 @@ class TLTDesc(ctypes.Structure):
         ("mt_tiles", c_void_p), ("mt_ptr", c_void_p), ("nmt", c_int), ("dim", c_int),
         ("cu", c_void_p), ("ncu", c_int), ("nparts_total", c_int), ("il", c_int), ("nar", TLNarrow),
         ("live", c_void_p), ("live_mt", c_void_p),
+        ("groups", c_void_p), ("ngroups", c_int), ("live_g", c_void_p),     # tile groups (ops/tiled.py), 24 ints each
     ]
 
 

@@ -45,6 +45,27 @@ the unit's index: the kernel sums a sub-block's pair exactly as the row-block ke
 shard's loss does not depend on the unit height, bit for bit. The kernel (``tl_fwd_tall_block``) keeps ONE fp64 accumulator row of
 4096 slots per work-group: wave k walks sub-block k's narrow rounds, then one wave walks the wide section.
 
+TILE GROUPS (``PML_TL_TGROUP=0/1`` or ``tgroup=``; by default, ``shard_tgroup``: bf16 / fp32 shards in the
+interleaved + narrow layout with 1024-column tiles, chunks whose rows fit 20 bits, ``dim >= 2^16`` and at least 96
+full chunks -- smaller shards are slower with them, ``profiles/tl_t_groups.md``; fp64 shards and the 2048-column
+tiles of sparse shards keep the items above): the mirror image of the tall forward units. A GROUP is four consecutive tiles ``4g .. 4g+3`` of a
+transpose chunk in which every non-empty tile has exactly one item; split (hot) tiles, their quadruples and the
+leftover tiles keep their items and ``tl_t_item``. The narrow rounds are built per tile exactly as above and stay
+where they are. The entries that stay wide are MERGED per group into FOUR sub-windows: an entry goes to sub-window q
+when ``tl_t_item``'s wave q would walk its round (round r of a tile with nr wide rounds: ``nr q / 4 <= r <
+nr (q + 1) / 4``), and a sub-window is sorted by (row, column in group), packed ``(local_row << 12) | col12``,
+lane-interleaved and padded to whole rounds. Entries are moved, not duplicated, and up to four tiles' pad rounds
+become one. A wide gather then reads the per-row values of four tiles' entries: 0.41 instead of 0.53 distinct 64-byte
+lines per wide entry in such tiles (``scripts/tl_tail_lines.py --transpose``). Restricted to one column, a sub-window
+holds that column's entries of quarter q in row order, so the kernel (``tl_t_group``: one fp64 accumulator row of
+4096 slots, for q = 0..3 the four tiles' narrow quarters q, then sub-window q, then ``tot = q ? tot + acc : acc``)
+performs the additions of ``tl_t_item`` in its order and grouping and the results are the ungrouped layout's BIT FOR
+BIT. Group table (``groups``, 24 ints): ``{tile0, part[4], n_lo[4], n_hi[4], e_lo[4], e_hi[4], chunk, row_base,
+-}``; ``part`` = -1 (add into G), a partial-row slot (shard-wide tables: the slot the tile's item would have, so
+the combine is unchanged) or ``TG_EMPTY`` for a tile without entries. ``items`` holds the remaining items only;
+:meth:`TLTChunk.unit_tiles` / ``unit_counts`` / ``logical`` list the items, then the groups' tiles. Readers that walk
+items (column statistics, row-sampled copies) take :meth:`TLTChunk.ungrouped`.
+
 Both copies are stored LANE-INTERLEAVED by default (``il``; ``PML_TL_IL=0`` keeps the plain order): every work
 unit (forward block / transpose item) starts on a 256-entry round boundary and is zero-padded to whole rounds,
 and inside a round the 16-B quad of lane L holds the unit's sorted entries L, L+64, L+128, L+192, so each gather
@@ -124,6 +145,17 @@ TALL_BITS = 12           # rows of a tall unit (2^12 fp64 sums = 32 KB of LDS pe
 TALL_SUB_BITS = 10       # rows of its sub-blocks: the slot bits of the narrow rounds' 16-bit packs
 TALL_MIN_DIM = 1 << 16
 TALL_COLS = 10           # ints per row of a tall unit table
+# Tile groups (TLTChunk, "TILE GROUPS" above): PML_TL_TGROUP=0/1 (read when a chunk is built) overrides the rule.
+# Engaged per SHARD (shard_tgroup): bit-for-bit equal results; on the 125M-row headline 33.38-33.48 vs 34.14-34.18
+# ms/step (three alternated runs each), neutral at 62.5M rows and SLOWER on small shards, whose few groups are long
+# one-wave units that leave CUs idle (16M rows: 5.76 vs 4.88 ms/step, 3M rows: 2.83 vs 1.27); profiles/tl_t_groups.md.
+TGROUP_DEFAULT = True    # False: only PML_TL_TGROUP=1 / the constructor argument
+TG_MIN_CHUNKS = 96       # full chunks of a shard for the groups to engage on their own (~22K groups at the bench shape)
+TG_BITS = 12             # columns of a tile group (2^12 fp64 sums = 32 KB of LDS per work-group)
+TG_SUB_BITS = 10         # columns of its tiles
+TG_MIN_DIM = 1 << 16
+TG_COLS = 24             # ints per row of a group table
+TG_EMPTY = -2            # ``part`` of a group's tile without entries (nothing is written for it)
 
 
 def narrow_width(sbits: int) -> int:
@@ -370,6 +402,29 @@ def tall_engages(tall: Optional[bool], dim: int, m: int, dtype, il: int, want_rb
     return bool(tall)
 
 
+def tgroup_engages(tgroup: Optional[bool], dim: int, chunk_rows: int, dtype, il: int, cbits: int) -> bool:
+    """Whether a transpose chunk is built with tile groups (module docstring, TILE GROUPS). The layout can hold
+    bf16 / fp32 chunks in the interleaved + narrow layout with 1024-column tiles whose rows fit ``32 - 12`` bits
+    (fp64 shards and the 2048-column tiles of sparse shards keep their items), and then only when asked for: by
+    ``tgroup`` (constructor; the shard builders pass :func:`shard_tgroup`) or ``PML_TL_TGROUP``."""
+    if not (il and NARROW and dtype != torch.float64 and cbits == TG_SUB_BITS
+            and _bits(chunk_rows) + TG_BITS <= 32):
+        return False
+    if tgroup is None and os.environ.get("PML_TL_TGROUP") is not None:
+        tgroup = bool(int(os.environ["PML_TL_TGROUP"]))
+    return bool(tgroup)
+
+
+def shard_tgroup(dim: int, n_rows: int, chunk_rows: int) -> Optional[bool]:
+    """One choice for every transpose chunk of a shard: wide feature spaces (``dim >= 2^16``) and at least
+    ``TG_MIN_CHUNKS`` full chunks -- a group is a long unit (four tiles walked by one work-group, their wide entries by
+    one wave at a time), and a shard with few of them leaves CUs idle (module constants). None (``PML_TL_TGROUP``
+    decides) when that is set."""
+    if os.environ.get("PML_TL_TGROUP") is not None:
+        return None
+    return bool(TGROUP_DEFAULT and dim >= TG_MIN_DIM and n_rows >= TG_MIN_CHUNKS * chunk_rows)
+
+
 def shard_tall(dim: int, chunk_rows: int) -> Optional[bool]:
     """One choice for every chunk of a shard (the shard-wide forward launch needs one unit height): the rule applied
     to the shard's widest column window and to its full chunks, so a short last chunk follows the others (a ragged
@@ -600,10 +655,14 @@ class TLTChunk(_NarrowMixin):
     kind = "tl"
 
     def __init__(self, rowptr: torch.Tensor, col: torch.Tensor, val: torch.Tensor, dim: int, chunk_rows: int,
-                 cbits: Optional[int] = None, item_entries: Optional[int] = None, il: Optional[int] = None):
+                 cbits: Optional[int] = None, item_entries: Optional[int] = None, il: Optional[int] = None,
+                 tgroup: Optional[bool] = None):
+        """``tgroup``: True / False force the tile-group layout on / off (where the layout can hold the chunk at
+        all); None: ``PML_TL_TGROUP``, else the rule of :func:`tgroup_engages`."""
         self.il = INTERLEAVE if il is None else int(il)
         if item_entries is None:
             item_entries = int(os.environ.get("PML_TL_ITEM_ENTRIES", DEFAULT_ITEM_ENTRIES))
+        self._chunk_rows, self._item_entries = chunk_rows, item_entries
         dev = val.device
         rowptr = rowptr.to(dev, torch.int64)
         col = col.to(dev, torch.int64)
@@ -654,17 +713,45 @@ class TLTChunk(_NarrowMixin):
         items = np.column_stack([it_tile, lo, hi, part_of]).astype(np.int64).reshape(-1, 4)
         items = np.column_stack([items, np.zeros((len(items), 2), np.int64)])
         self._sbits, self._ew = self.cbits, (1, 2)
+        # tile groups: complete quadruples of tiles 4g .. 4g+3 whose non-empty tiles all have one item
+        gsel = np.zeros(len(items), dtype=bool)
+        gok = np.zeros(0, dtype=bool)
+        if len(items) and ntiles >= 4 and tgroup_engages(tgroup, dim, max(chunk_rows, m), val.dtype, self.il,
+                                                          self.cbits):
+            k_of_tile = np.zeros(ntiles, np.int64)
+            k_of_tile[nz] = n_it
+            gok = k_of_tile[: (ntiles >> 2) << 2].reshape(-1, 4).max(1) == 1
+            g_of_item = items[:, 0] >> 2
+            gsel = (g_of_item < len(gok)) & gok[np.minimum(g_of_item, len(gok) - 1)]
+        groups = np.zeros((0, TG_COLS), np.int64)
         if self.il:
             cnt = torch.from_numpy(items[:, 2] - items[:, 1]).to(dev)
             wp, wv, wn, npk, nvl, nbs, nr = split_narrow(pack.to(torch.int64) & 0xFFFFFFFF, val, cnt, self.cbits, m)
             del pack, val
-            self.pack, self.val, new_lo = _interleave(_to_u32_bits(wp), wv, wn)
-            del wp, wv
-            items[:, 1] = new_lo.cpu().numpy()
-            items[:, 2] = items[:, 1] + wn.cpu().numpy()
             nr = nr.cpu().numpy()
             items[:, 5] = np.cumsum(nr)
             items[:, 4] = items[:, 5] - nr
+            if gsel.any():
+                wp, wv, wn, gcnt = self._merge_groups(wp, wv, wn, items[:, 0], gsel, len(gok))
+                gidx = np.flatnonzero(gok)
+                groups = np.zeros((len(gidx), TG_COLS), np.int64)
+                it_of_tile = np.full(ntiles, -1, np.int64)
+                it_of_tile[items[gsel, 0]] = np.flatnonzero(gsel)
+                it4 = it_of_tile[gidx[:, None] * 4 + np.arange(4)[None, :]]
+                groups[:, 0] = gidx * 4
+                groups[:, 1:5] = np.where(it4 >= 0, -1, TG_EMPTY)
+                groups[:, 5:9] = np.where(it4 >= 0, items[it4, 4], 0)
+                groups[:, 9:13] = np.where(it4 >= 0, items[it4, 5], 0)
+                items = items[~gsel]
+            self.pack, self.val, new_lo = _interleave(_to_u32_bits(wp), wv, wn)
+            del wp, wv
+            new_lo, wn = new_lo.cpu().numpy(), wn.cpu().numpy()
+            items[:, 1] = new_lo[: len(items)]
+            items[:, 2] = items[:, 1] + wn[: len(items)]
+            if len(groups):
+                groups[:, 13:17] = new_lo[len(items):].reshape(-1, 4)
+                groups[:, 17:21] = groups[:, 13:17] + wn[len(items):].reshape(-1, 4)
+            self.nitems = len(items)
         else:
             self.pack, self.val = _pad(pack), _pad(val.contiguous())
             npk, nvl, nbs = _empty_narrow(val)
@@ -675,9 +762,53 @@ class TLTChunk(_NarrowMixin):
         self.mt_ptr = torch.tensor(np.asarray(mt_ptr, dtype=np.int32), device=dev)
         self.cu = torch.tensor(np.asarray(cu if len(cu) else [(0, 0, 0)], dtype=np.int32).reshape(-1, 3), device=dev)
         self.m, self.nnz, self.dim = m, nnz, dim
+        self.ngroups = len(groups)
+        self.groups = torch.tensor(groups.astype(np.int32), device=dev).reshape(-1, TG_COLS)
+        self._make_desc()
+
+    def _make_desc(self):
         self.desc = TLTDesc(self.items.data_ptr(), self.nitems, self.cbits, self.pack.data_ptr(),
-                            self.val.data_ptr(), self.mt_tiles.data_ptr(), self.mt_ptr.data_ptr(), self.nmt, dim,
-                            self.cu.data_ptr(), self.ncu, self.nparts, self.il, self.nar)
+                            self.val.data_ptr(), self.mt_tiles.data_ptr(), self.mt_ptr.data_ptr(), self.nmt, self.dim,
+                            self.cu.data_ptr(), self.ncu, self.nparts, self.il, self.nar,
+                            groups=self.groups.data_ptr() if self.ngroups else None, ngroups=self.ngroups)
+
+    @staticmethod
+    def _merge_groups(wp, wv, wn, tile_of_item, gsel, ngroups_all):
+        """Move the wide entries of the grouped items (``gsel``) behind those of the other items, merged per group
+        into four sub-windows: an entry goes to the sub-window of its QUARTER, the wave of ``tl_t_item`` that walks
+        its round today (round r of an item with nr wide rounds: wave (4 r + 3) // nr, i.e. nr w / 4 <= r <
+        nr (w + 1) / 4), and a sub-window is sorted by (row, column in group), packed ``(row << 12) | col12``.
+        Returns the new streams, the entries per unit (the remaining items, then 4 sub-windows per group that
+        holds entries) and the sub-window counts."""
+        dev = wp.device
+        S, T = TG_SUB_BITS, TG_BITS
+        gs = torch.from_numpy(gsel).to(dev)
+        n_items = wn.numel()
+        tot = int(wn.sum())
+        item = torch.repeat_interleave(torch.arange(n_items, device=dev), wn, output_size=tot)
+        eg = gs[item]
+        it_g = item[eg]
+        j = torch.arange(tot, device=dev)[eg] - (torch.cumsum(wn, 0) - wn)[it_g]
+        del item
+        nrw = (wn + IL_ROUND - 1) // IL_ROUND
+        quarter = (4 * (j // IL_ROUND) + 3) // nrw[it_g]
+        tile = torch.from_numpy(np.ascontiguousarray(tile_of_item)).to(dev)[it_g]
+        del j, it_g
+        p = wp[eg]
+        p12 = ((p >> S) << T) | ((tile & 3) << S) | (p & ((1 << S) - 1))
+        win = (tile >> 2) * 4 + quarter
+        del p, tile, quarter
+        skey = (win << 32) | p12
+        order = torch.sort(skey, stable=True).indices
+        del skey
+        gp, gv = p12[order], wv[eg][order]
+        bounds = torch.searchsorted(win[order].contiguous(), torch.arange(4 * ngroups_all + 1, device=dev))
+        wcnt = (bounds[1:] - bounds[:-1]).view(-1, 4)
+        gok = torch.zeros(ngroups_all, dtype=torch.bool, device=dev)
+        gok[torch.from_numpy(np.unique(tile_of_item[gsel] >> 2)).to(dev)] = True
+        gcnt = wcnt[gok].reshape(-1)
+        keep = ~eg
+        return (torch.cat([wp[keep], gp]), torch.cat([wv[keep], gv]), torch.cat([wn[~gs], gcnt]), gcnt)
 
     @property
     def parts_needed(self) -> int:
@@ -689,7 +820,73 @@ class TLTChunk(_NarrowMixin):
 
     def nbytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in (self.items, self.mt_tiles, self.mt_ptr, self.cu, self.pack,
-                                                           self.val, self.npack, self.nval, self.nbase))
+                                                           self.val, self.npack, self.nval, self.nbase, self.groups))
+
+    # the UNITS of a chunk with tile groups: its items, then the four tiles of every group (a tile without entries
+    # is a unit of none)
+    def unit_tiles(self) -> torch.Tensor:
+        t = self.items[:, 0].to(torch.int64)
+        if not self.ngroups:
+            return t
+        g0 = self.groups[:, 0].to(torch.int64)
+        return torch.cat([t, (g0[:, None] + torch.arange(4, device=t.device)[None, :]).reshape(-1)])
+
+    def unit_counts(self) -> torch.Tensor:
+        c = super().unit_counts()
+        if not self.ngroups:
+            return c
+        return torch.cat([c, self._group_units()[3]])
+
+    def narrow_table(self) -> torch.Tensor:
+        """int64 rows {tile, 0, 0, 0, n_lo, n_hi} of the items and of the groups' tiles in the narrow section's
+        storage order (tile order; the items of a split tile in item order)."""
+        t = self.items[: self.nitems].to(torch.int64)
+        if not self.ngroups:
+            return t
+        g = self.groups.to(torch.int64)
+        gt = torch.zeros((4 * g.shape[0], 6), dtype=torch.int64, device=t.device)
+        gt[:, 0] = (g[:, :1] + torch.arange(4, device=t.device)[None, :]).reshape(-1)
+        gt[:, 4], gt[:, 5] = g[:, 5:9].reshape(-1), g[:, 9:13].reshape(-1)
+        gt = gt[g[:, 1:5].reshape(-1) != TG_EMPTY]
+        allt = torch.cat([t[:, :6], gt])
+        return allt[torch.sort(allt[:, 0], stable=True).indices]
+
+    @property
+    def n_narrow_rounds(self) -> int:
+        g = self.groups.to(torch.int64)
+        return _NarrowMixin.n_narrow_rounds.fget(self) + (int((g[:, 9:13] - g[:, 5:9]).sum()) if self.ngroups else 0)
+
+    def _group_units(self):
+        """(unit, pack, val, counts) of the groups' entries in unit order (unit = 4 x group + tile in group; per
+        unit its narrow entries, then its wide entries in stored order), packs as ``(row << cbits) | column in
+        tile``; cached."""
+        if getattr(self, "_gunits", None) is not None:
+            return self._gunits
+        S, T = TG_SUB_BITS, TG_BITS
+        g = self.groups.to(torch.int64)
+        dev = g.device
+        G = g.shape[0]
+        wcnt = (g[:, 17:21] - g[:, 13:17]).reshape(-1)
+        ph = il_phys(g[:, 13:17].reshape(-1), wcnt).to(self.pack.device)
+        wp = (self.pack[ph].to(torch.int64) & 0xFFFFFFFF).to(dev)
+        wv = self.val[ph].to(dev)
+        gw = torch.repeat_interleave(torch.arange(4 * G, device=dev), wcnt) >> 2
+        unit_w = gw * 4 + ((wp >> S) & 3)
+        wp = ((wp >> T) << S) | (wp & ((1 << S) - 1))
+        n_lo, nn = g[:, 5:9].reshape(-1), (g[:, 9:13] - g[:, 5:9]).reshape(-1) * IL_ROUND
+        if int(nn.sum()):
+            npk, nvl = narrow_logical(self.npack, self.nval, self.nbase, 0, int(g[:, 9:13].max()), S)
+            unit_n = torch.repeat_interleave(torch.arange(4 * G, device=dev), nn)
+            pos = n_lo[unit_n] * IL_ROUND + torch.arange(int(nn.sum()), device=dev) - (torch.cumsum(nn, 0) - nn)[unit_n]
+            unit = torch.cat([unit_n, unit_w])
+            order = torch.sort(unit, stable=True).indices
+            unit, pk, vl = unit[order], torch.cat([npk[pos], wp])[order], torch.cat([nvl[pos], wv])[order]
+        else:
+            order = torch.sort(unit_w, stable=True).indices
+            unit, pk, vl = unit_w[order], wp[order], wv[order]
+        b = torch.searchsorted(unit.contiguous(), torch.arange(4 * G + 1, device=dev))
+        self._gunits = (unit, pk, vl, b[1:] - b[:-1])
+        return self._gunits
 
     def window(self, e_lo: int, e_hi: int):
         """(pack, val) of one item's wide window in sorted order."""
@@ -699,16 +896,47 @@ class TLTChunk(_NarrowMixin):
         return self.pack[ph], self.val[ph]
 
     def logical(self):
+        """(pack, val) of the non-zeros in unit order (:meth:`unit_tiles` / :meth:`unit_counts`: the items, then the
+        tiles of the groups), packs ``(row << cbits) | column in tile``."""
         if not self.il:
             return self.pack[: self.nnz], self.val[: self.nnz]
         ph = il_phys(self.items[:, 1], self.items[:, 2] - self.items[:, 1])
-        return self._logical_all(self.pack[ph], self.val[ph])
+        pk, vl = self._logical_all(self.pack[ph], self.val[ph])
+        if not self.ngroups:
+            return pk, vl
+        _, gp, gv, _ = self._group_units()
+        return torch.cat([pk.to(torch.int64) & 0xFFFFFFFF, gp]), torch.cat([vl, gv])
+
+    def coo(self):
+        """(row, col, val) of the chunk's non-zeros sorted by (row, column)."""
+        pk, vl = self.logical()
+        p = pk.to(torch.int64) & 0xFFFFFFFF
+        tile = torch.repeat_interleave(self.unit_tiles(), self.unit_counts())
+        key = ((p >> self.cbits) << 32) | (tile << self.cbits) | (p & ((1 << self.cbits) - 1))
+        key, order = torch.sort(key, stable=True)
+        return key >> 32, key & 0xFFFFFFFF, vl[order]
+
+    def ungrouped(self, cache: bool = True) -> "TLTChunk":
+        """This chunk without tile groups, for the readers that walk items only (column statistics, row-sampled
+        copies): rebuilt from the stored entries, so it is the chunk that ``tgroup=False`` would have built (cached;
+        a chunk without groups is returned as is)."""
+        if not self.ngroups:
+            return self
+        twin = getattr(self, "_ungrouped", None)
+        if twin is None:
+            row, col, val = self.coo()
+            rowptr = torch.searchsorted(row.contiguous(), torch.arange(self.m + 1, device=row.device))
+            twin = TLTChunk(rowptr, col, val, self.dim, self._chunk_rows, cbits=self.cbits,
+                            item_entries=self._item_entries, il=self.il, tgroup=False)
+            if cache:
+                self._ungrouped = twin
+        return twin
 
     def emulate_rmatvec(self, r: torch.Tensor, square: bool = False) -> torch.Tensor:
         pk, vl = self.logical()
         p = pk.to(torch.int64) & 0xFFFFFFFF
         row = p >> self.cbits
-        tile_of_entry = torch.repeat_interleave(self.items[:, 0].to(torch.int64), self.unit_counts())
+        tile_of_entry = torch.repeat_interleave(self.unit_tiles(), self.unit_counts())
         col = (tile_of_entry << self.cbits) + (p & ((1 << self.cbits) - 1))
         v = vl.to(torch.float64)
         if square:
@@ -739,17 +967,39 @@ class TLTMulti:
         self.il = chunks[0].il
         if any(ch.il != self.il for ch in chunks):
             raise ValueError("TLTMulti: chunks mix interleaved and plain streams")
-        its = []
+        # rows: the items of a chunk, then one row per non-empty tile of its tile groups (column 7: -1 for an item,
+        # else 4 x the group's row in ``grp`` + the tile's number in the group) -- such a tile counts as an item of
+        # its tile, so the partial-row slots and the combine tables are those of the same shard without groups
+        its, grps = [], []
+        n_grp = 0
         for c, ch in enumerate(chunks):
             it = ch.items[: ch.nitems].cpu().numpy().astype(np.int64).reshape(-1, 6)
             toff = 0 if tile_offsets is None else int(tile_offsets[c])
             its.append(np.column_stack([np.full(len(it), c), it[:, 0] + toff, it[:, 1], it[:, 2],
-                                        np.full(len(it), row_starts[c]), it[:, 4], it[:, 5]]))
-        it = np.concatenate(its) if its else np.zeros((0, 7), np.int64)
-        src_all = np.arange(len(it))
+                                        np.full(len(it), row_starts[c]), it[:, 4], it[:, 5], np.full(len(it), -1)]))
+            if getattr(ch, "ngroups", 0):
+                g = ch.groups.cpu().numpy().astype(np.int64).reshape(-1, TG_COLS).copy()
+                g[:, 0] += toff
+                g[:, 21], g[:, 22], g[:, 23] = c, row_starts[c], np.arange(len(g))
+                gi, k = np.nonzero(g[:, 1:5] != TG_EMPTY)
+                z = np.zeros(len(gi), np.int64)
+                its.append(np.column_stack([z + c, g[gi, 0] + k, z, z, z + row_starts[c], z, z,
+                                            4 * (n_grp + gi) + k]))
+                grps.append(g)
+                n_grp += len(g)
+        it = np.concatenate(its) if its else np.zeros((0, 8), np.int64)
+        grp = np.concatenate(grps) if grps else np.zeros((0, TG_COLS), np.int64)
+        real = it[:, 7] < 0
+        src_all = np.cumsum(real) - 1                      # a real row's index into the chunks' concatenated items
         if tile_range is not None:
             in_range = (it[:, 1] >= tile_range[0]) & (it[:, 1] < tile_range[1])
+            gin = np.zeros(len(grp), np.int64)
+            np.add.at(gin, it[~real, 7] >> 2, np.where(in_range[~real], 1, 1 << 20))
+            if np.any((gin % (1 << 20) > 0) & (gin >= (1 << 20))):
+                raise ValueError("TLTMulti: tile_range cuts a tile group (round the range to multiples of 4 tiles)")
             it = it[in_range]
+            src_all = src_all[in_range]
+            real = real[in_range]
         n = len(it)
         tile = it[:, 1]
         order = np.lexsort((np.arange(n), tile))          # grouped by tile, (chunk, item) order inside
@@ -767,10 +1017,18 @@ class TLTMulti:
         u_tile = np.repeat(np.arange(len(km)), nu)
         u_first = np.repeat(plo, nu) + np.repeat(sg, nu) * (np.arange(int(nu.sum())) - np.repeat(np.cumsum(nu) - nu, nu))
         u_last = np.minimum(u_first + np.repeat(sg, nu), np.repeat(plo + km, nu))
-        self.nitems, self.nparts, self.ncu, self.nmt = n, int(km.sum()), int(nu.sum()), len(km)
+        self.nparts, self.ncu, self.nmt = int(km.sum()), int(nu.sum()), len(km)
+        # the group tiles' slots go to their group rows; the launch table holds the items only
+        slot = it[~real, 7]
+        grp[slot >> 2, 1 + (slot & 3)] = part[~real]
+        used = np.zeros(len(grp), dtype=bool)
+        used[slot >> 2] = True
+        grp = grp[used]
+        it, part, src = it[real], part[real], src_all[real]
+        n = len(it)
+        self.nitems, self.ngroups = n, len(grp)
         rows = np.column_stack([it[:, 0], it[:, 1], it[:, 2], it[:, 3], part, it[:, 4], it[:, 5],
                                 it[:, 6]]).astype(np.int32)
-        src = src_all if tile_range is None else src_all[in_range]
         if XCD_GROUPS > 1 and n > XCD_GROUPS:
             xo = xcd_order(it[:, 0], XCD_GROUPS)
             rows, src = rows[xo], src[xo]
@@ -782,9 +1040,13 @@ class TLTMulti:
                                if self.ncu else np.zeros((1, 3), np.int32), device=dev)
         self.ptrs = stream_ptr_table(chunks, dev)
         self._chunks = list(chunks)  # keep the streams alive
+        # group rows as the chunks' (TG_COLS ints; tile0 global, the tiles' shard-wide slots, [21] chunk, [22] row
+        # base); [23], the group's row in its chunk's table, is for the host emulation
+        self.groups = torch.tensor(grp.astype(np.int32), device=dev).reshape(-1, TG_COLS)
         self.desc = TLTMultiDesc(self.items.data_ptr(), n, self.cbits, self.ptrs.data_ptr(),
                                  self.mt_tiles.data_ptr(), self.mt_ptr.data_ptr(), self.nmt, dim,
-                                 self.cu.data_ptr(), self.ncu, self.nparts, self.il)
+                                 self.cu.data_ptr(), self.ncu, self.nparts, self.il,
+                                 groups=self.groups.data_ptr() if self.ngroups else None, ngroups=self.ngroups)
 
     @property
     def parts_needed(self) -> int:
@@ -796,8 +1058,10 @@ class TLTMulti:
         partial-row slots and combine tables are shared. No host work beyond the pointer table."""
         import copy
         from .native import TLTMultiDesc
+        if self.ngroups or any(getattr(ch, "ngroups", 0) for ch in chunks):
+            raise ValueError("TLTMulti.restreamed: row-sampled copies are made of chunks without tile groups")
         dev = self.items.device
-        cat = torch.cat([ch.items[: ch.nitems].to(torch.int64) for ch in chunks]) if chunks else None
+        cat =torch.cat([ch.items[: ch.nitems].to(torch.int64) for ch in chunks]) if chunks else None
         rows = self.items.to(torch.int64).clone()
         if self.nitems:
             sel = cat[self._src]
@@ -833,6 +1097,23 @@ class TLTMulti:
                 G[tile * C:(tile + 1) * C] += acc
             else:
                 parts[part] = acc
+        for g in self.groups.cpu().tolist():
+            ch = self._chunks[g[21]]
+            unit, pk, vl, cnt = ch._group_units()
+            ends = torch.cumsum(cnt, 0).cpu().tolist()
+            for k in range(4):
+                part, u = g[1 + k], 4 * g[23] + k
+                if part == TG_EMPTY:
+                    continue
+                p = pk[ends[u] - int(cnt[u]):ends[u]].cpu()
+                v = vl[ends[u] - int(cnt[u]):ends[u]].cpu().to(torch.float64)
+                if square:
+                    v = v * v
+                acc = torch.zeros(C, dtype=torch.float64).index_add_(0, p & (C - 1), v * r[g[22] + (p >> self.cbits)])
+                if part < 0:
+                    G[(g[0] + k) * C:(g[0] + k + 1) * C] += acc
+                else:
+                    parts[part] = acc
         cu = self.cu.cpu().tolist()
         l1 = [parts[a:b].sum(0) for _, a, b in cu[: self.ncu]]
         mp = self.mt_ptr.cpu().tolist()
@@ -900,6 +1181,8 @@ class RowCompaction:
         from .native import CmpArgs, check, require_game_lib, stream_handle
         if not ch.il:
             raise ValueError("row-sampled copies need the interleaved layout")
+        if getattr(ch, "ngroups", 0):
+            raise ValueError("row-sampled copies are made of a transpose chunk's ungrouped() copy")
         self.ch, self.keep, self.forward = ch, keep, forward
         dev = ch.pack.device
         self.filter_narrow = bool(filter_narrow)

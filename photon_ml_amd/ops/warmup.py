@@ -60,6 +60,12 @@ def runtime_warmup(device, force: bool = False) -> float:
     tiny.matvec(torch.zeros(5, dtype=torch.float64, device=dev))
     z = torch.zeros(8, dtype=torch.float64, device=dev)
     tiny._fwd(0, torch.zeros(5, dtype=torch.float32, device=dev), 0, 0, 0.0, None, None, z_out=z, stats=False)
+    # the tile-group transpose family (tl_tg_*): one group of 4 tiles x 2 entries, per-chunk and shard-wide
+    tiny = DeviceGLMData.from_device_csr(torch.arange(0, 18, 2, device=dev), (i[:16] * 512) % 4096,
+                                         x[:16].to(torch.float32), torch.zeros(8), torch.zeros(8), torch.ones(8), 4096,
+                                         dev, "f32", tgroup=True)
+    tiny.rmatvec(torch.zeros(8, dtype=torch.float64, device=dev), build_multi=False)
+    tiny.rmatvec(torch.zeros(8, dtype=torch.float64, device=dev))
     key_histogram(i % 13, 13)                                            # libpml_game
     csr_gather_rows(torch.tensor([0, 2], dtype=torch.int64, device=dev), i[:2], x[:2],
                     torch.zeros(1, dtype=torch.int64, device=dev), torch.tensor([0, 4], dtype=torch.int64, device=dev))
