@@ -512,8 +512,10 @@ class RandomEffectCoordinate(Coordinate):
     def _full_variance_segmented(self, W: torch.Tensor, l2: float) -> torch.Tensor:
         """``(H_e^-1)_jj`` of every entity at ``W`` (packed like the coefficients). The curvature comes from one
         forward pass at the solution, as the SIMPLE Hessian diagonal's does; entities without active rows get
-        ``1 / l2``. On the GPU: ``SegmentedFullVariance`` (HIP routes for ``min(n_e, d_e) <= 128``, torch beyond);
-        on the CPU the torch definition for every entity."""
+        ``1 / l2``. On the GPU: ``SegmentedFullVariance`` (LDS-resident HIP routes for ``min(n_e, d_e) <= 128``, the
+        blocked HIP route up to 1024 unless ``PML_VAR_BLOCKED=0``, torch beyond); on the CPU the torch definition for
+        every entity."""
+        from ..ops.native import VAR_BLOCKED_MMAX
         from ..optimization.variance import SegmentedFullVariance, segmented_full_variance
         ds = self.dataset
         seg = ds.seg
@@ -524,7 +526,8 @@ class RandomEffectCoordinate(Coordinate):
         if seg.y.device.type == "cuda":
             plan = getattr(self, "_var_plan", None)
             if plan is None:
-                plan = self._var_plan = SegmentedFullVariance(seg.row_ptr, seg.col_ptr, csr)
+                blocked = 0 if os.environ.get("PML_VAR_BLOCKED", "1") == "0" else VAR_BLOCKED_MMAX
+                plan = self._var_plan = SegmentedFullVariance(seg.row_ptr, seg.col_ptr, csr, blocked_mmax=blocked)
             var, stats = plan.compute(c, l2)
         else:
             var, n = segmented_full_variance(seg.row_ptr, seg.col_ptr, csr, c, l2)

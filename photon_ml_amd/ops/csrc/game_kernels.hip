@@ -17,6 +17,9 @@
 //   stream (plain AUC under a process group: every rank counts the score bucket it received).
 // * var_normal_kernel / var_scale_gram_kernel / chol_colnorm_kernel -- FULL coefficient variances diag(H_e^-1) of the
 //   random-effect entities: per-entity normal matrix, then squared column norms of G^-1 R from its Cholesky factor.
+// * var_blk_normal_kernel / var_blk_gram_kernel / blocked_chol_kernel / blocked_trinv_kernel /
+//   var_blk_colnorm_kernel -- the same for factor orders 129 .. 1024: matrices in a global workspace, one work-group
+//   per entity, Cholesky and triangular inverse blocked in 16-column panels on the fp64 matrix cores.
 //
 // Built with: hipcc --offload-arch=gfx950 -O3 -shared -fPIC (photon_ml_amd/ops/build.py). C ABI, ctypes.
 
@@ -653,6 +656,562 @@ __global__ __launch_bounds__(64) void chol_colnorm_kernel(int B, int n, const do
     }
     if (j < ncols) out[cb + j] = MODE ? (1.0 - q) / lam : q;
     __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Blocked FULL-variance route for VAR_MMAX < m <= VAR_BLOCKED_MMAX: the same two routes, the matrices in a global
+// workspace A [chunk, n, n] (L2 / MALL resident) and one work-group of VB_WAVES waves per entity:
+//   var_blk_normal_kernel / var_blk_gram_kernel   A (lower triangle; strict upper triangle zero; padding identity)
+//   blocked_chol_kernel                           A = G G^T in place, 16-column panels, fp64 MFMA
+//   blocked_trinv_kernel                          T = G^-1 in place (forward substitution with identity panels, which
+//                                                 are zero above their first row: only the lower triangle is formed)
+//   var_blk_colnorm_kernel                        primal: q_j = sum_k T[k][j]^2; row space: q_j = |T b_j|^2 with
+//                                                 T b = sparse combinations of the CSR rows (no dense Y is formed)
+// No atomics; every address has one owning wave (or thread) per step and a fixed summation order.
+// ---------------------------------------------------------------------------------------------------------------
+#define VAR_BLOCKED_MMAX 1024
+#define VAR_BLOCKED_DMAX 2048   // row-space route: widest entity (LDS images of d_e doubles per wave / per row)
+#define VB_WAVES 8
+#define VB_THREADS (64 * VB_WAVES)
+#define VB_T 16                 // panel width = MFMA tile
+#define VBN_U 8                 // var_blk_normal_kernel: own entries of a row updated per round (loads in flight)
+#define VBC_R 8                 // var_blk_colnorm_kernel<1>: CSR rows per round (loads in flight)
+
+// leading dimension (doubles) of a 16-row LDS operand of up to n columns: = 2 (mod 32), so the 32 lanes of one
+// ds_read_b64 half (16 rows x 2 k) fall on 32 distinct 8-byte bank pairs
+__host__ __device__ inline int vb_ld(int n) { return ((n + 31) / 32) * 32 + 2; }
+
+__device__ __forceinline__ void vb_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// One wave: in-place Cholesky of the 16 x 16 block sD ([16][17], lower triangle) whose first w rows / columns are
+// live (the rest: identity). Returns 0, or j + 1 for the first non-positive / non-finite pivot (wave-uniform).
+__device__ int vb_chol16(double* sD, int w, int lane) {
+  const int r = lane & 15, q = lane >> 4;
+  for (int j = 0; j < VB_T; ++j) {
+    vb_wave_sync();
+    const double d = sD[j * 17 + j];
+    if (j < w && (!(d > 0.0) || !isfinite(d))) return j + 1;
+    const double l = sqrt(d);
+    const double lrj = sD[r * 17 + j] / l;
+    vb_wave_sync();
+    if (q == 0) {
+      if (r > j) sD[r * 17 + j] = lrj;
+      else if (r == j) sD[r * 17 + j] = l;
+    }
+    vb_wave_sync();
+    for (int c = j + 1 + q; c < VB_T; c += 4)
+      if (r >= c) sD[r * 17 + c] = fma(-sD[r * 17 + j], sD[c * 17 + j], sD[r * 17 + c]);
+  }
+  vb_wave_sync();
+  return 0;
+}
+
+// One wave: sI [16][16] = inverse of the lower-triangular block sD ([16][17]); lane c < 16 solves column c.
+__device__ void vb_inv16(const double* sD, double* sI, int lane) {
+  if (lane < VB_T) {
+    double x[VB_T];
+#pragma unroll
+    for (int p = 0; p < VB_T; ++p) {
+      double s = p == lane ? 1.0 : 0.0;
+#pragma unroll
+      for (int k = 0; k < p; ++k) s = fma(-sD[p * 17 + k], x[k], s);
+      x[p] = s / sD[p * 17 + p];
+    }
+#pragma unroll
+    for (int p = 0; p < VB_T; ++p) sI[p * VB_T + lane] = p >= lane ? x[p] : 0.0;
+  }
+  vb_wave_sync();
+}
+
+// Primal normal matrix A = lam I + sum_i c_i x_i x_i^T (d_e <= n <= VAR_BLOCKED_MMAX) in the workspace slab of the
+// entity. Wave w owns the output rows hi = w (mod VB_WAVES): every wave walks all rows of the entity (each stages the
+// row in its own LDS slice) and adds the pairs (a, b <= a) of its own entries a -- the columns of a row increase, so
+// col_b <= col_a and only the lower triangle is touched. A long entity's rows are thereby shared by all waves without
+// a work-group barrier; one output address is only ever updated by one wave, in row order.
+__global__ __launch_bounds__(VB_THREADS) void var_blk_normal_kernel(int B, int n, const long long* __restrict__ ents,
+                                                                    const long long* __restrict__ row_ptr,
+                                                                    const long long* __restrict__ col_ptr,
+                                                                    const long long* __restrict__ nip,
+                                                                    const long long* __restrict__ pos,
+                                                                    const double* __restrict__ val,
+                                                                    const double* __restrict__ c, double lam,
+                                                                    double* A) {
+  extern __shared__ double vbn_lds[];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long long b = blockIdx.x;
+  if (b >= B) return;
+  const long long e = ents[b];
+  const long long r0 = row_ptr[e], r1 = row_ptr[e + 1];
+  const long long cb = col_ptr[e];
+  const long long dl = col_ptr[e + 1] - cb;
+  const int de = dl < n ? (int)(dl < 0 ? 0 : dl) : n;
+  const int per = n + (n + 1) / 2;                 // doubles per wave: values [n] + local columns [n] (int)
+  double* sv = vbn_lds + (size_t)w * per;
+  int* sc = (int*)(sv + n);
+  double* Ab = A + b * (long long)n * n;
+  for (int hi = w; hi < n; hi += VB_WAVES)
+    for (int j = lane; j < n; j += 64) Ab[(long long)hi * n + j] = hi == j ? (hi < de ? lam : 1.0) : 0.0;
+  vb_wave_sync();
+  // Two rows of look-ahead hide the chain row pointer -> entries -> output: (kA, rA, cA) are the pointers of row
+  // i + 1, (kB, rB, cB, colB, valB) row i with its first 64 entries (loaded from an index clamped to the entity's last
+  // entry, so the loads need no branch).
+  const long long klast = r1 > r0 ? nip[r1] - 1 : -1;
+  long long kA = 0, kB = 0, colB = 0;
+  int rA = 0, rB = 0;
+  double cA = 0.0, cB = 0.0, valB = 0.0;
+#define VBN_PTRS(I)                                   \
+  do {                                                \
+    if ((I) < r1) {                                   \
+      kA = nip[(I)];                                  \
+      const long long rl_ = nip[(I) + 1] - kA;        \
+      rA = rl_ < de ? (int)(rl_ < 0 ? 0 : rl_) : de;  \
+      cA = c[(I)];                                    \
+    } else {                                          \
+      rA = 0;                                         \
+    }                                                 \
+  } while (0)
+#define VBN_ENTRIES()                                           \
+  do {                                                          \
+    kB = kA; rB = rA; cB = cA;                                  \
+    const long long kc_ = kB + lane < klast ? kB + lane : klast; \
+    colB = pos[kc_] - cb;                                       \
+    valB = val[kc_];                                            \
+  } while (0)
+  if (klast < 0) return;                          // no entries: A = lam I
+  VBN_PTRS(r0);
+  VBN_ENTRIES();
+  VBN_PTRS(r0 + 1);
+  for (long long i = r0; i < r1; ++i) {
+    const double ci = cB;
+    const long long k0 = kB;
+    const int r = rB;
+    const long long col0 = colB;
+    const double val0 = valB;
+    VBN_ENTRIES();
+    VBN_PTRS(i + 2);
+    if (ci == 0.0 || r <= 0) continue;            // wave-uniform
+    vb_wave_sync();
+    if (lane < r) {
+      sc[lane] = (col0 >= 0 && col0 < de) ? (int)col0 : -1;
+      sv[lane] = val0;
+    }
+    for (int t = 64 + lane; t < r; t += 64) {
+      const long long col = pos[k0 + t] - cb;
+      sc[t] = (col >= 0 && col < de) ? (int)col : -1;
+      sv[t] = val[k0 + t];
+    }
+    vb_wave_sync();
+    const int lo0 = lane < r ? sc[lane] : -1;     // this lane's partner b = lane of every own entry a >= lane
+    const double vb0 = lane < r ? sv[lane] : 0.0;
+    for (int g0 = 0; g0 < r; g0 += 64) {
+      const int t = g0 + lane;
+      const int myc = t < r ? sc[t] : -1;
+      unsigned long long mine = __ballot(myc >= 0 && (myc % VB_WAVES) == w);
+      while (mine) {
+        // VBN_U own entries at a time: their rows differ, so all their loads go out before the first store
+        int a[VBN_U];
+        double* p[VBN_U];
+        double old[VBN_U];
+        bool on[VBN_U];
+#pragma unroll
+        for (int u = 0; u < VBN_U; ++u) {
+          a[u] = mine ? g0 + __builtin_ctzll(mine) : -1;
+          mine &= mine - 1;
+          on[u] = a[u] >= 0 && lane <= a[u] && lo0 >= 0;
+          // idle lanes read the slab's first element (one hot line): the loads need no branch between them
+          p[u] = on[u] ? Ab + (long long)sc[a[u] >= 0 ? a[u] : 0] * n + lo0 : Ab;
+          old[u] = *p[u];
+        }
+#pragma unroll
+        for (int u = 0; u < VBN_U; ++u)
+          if (on[u]) *p[u] = fma(ci * sv[a[u]], vb0, old[u]);
+#pragma unroll
+        for (int u = 0; u < VBN_U; ++u) {
+          if (a[u] < 64) continue;                // partners beyond the first 64 entries of a long row
+          double* row = Ab + (long long)sc[a[u]] * n;
+          const double va = ci * sv[a[u]];
+          for (int bb = 64 + lane; bb <= a[u]; bb += 64) {
+            const int lo = sc[bb];
+            if (lo >= 0) row[lo] = fma(va, sv[bb], row[lo]);
+          }
+        }
+      }
+    }
+  }
+#undef VBN_PTRS
+#undef VBN_ENTRIES
+}
+
+// Row-space normal matrix A = lam I + diag(s) X_e X_e^T diag(s), s = sqrt(c) (n_e <= n <= VAR_BLOCKED_MMAX,
+// d_e <= dcap <= VAR_BLOCKED_DMAX): rounds of 8 rows i whose scaled entries are scattered into an LDS image
+// [dcap][8]; thread j then walks row j once per round and forms the 8 dot products A[i][j], j <= i, in entry order.
+__global__ __launch_bounds__(VB_THREADS) void var_blk_gram_kernel(int B, int n, int dcap,
+                                                                  const long long* __restrict__ ents,
+                                                                  const long long* __restrict__ row_ptr,
+                                                                  const long long* __restrict__ col_ptr,
+                                                                  const long long* __restrict__ nip,
+                                                                  const long long* __restrict__ pos,
+                                                                  const double* __restrict__ val,
+                                                                  const double* __restrict__ c, double lam,
+                                                                  double* __restrict__ A) {
+  extern __shared__ double vbg_img[];              // [dcap][8]
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const long long b = blockIdx.x;
+  if (b >= B) return;
+  const long long e = ents[b];
+  const long long r0 = row_ptr[e];
+  const long long nl = row_ptr[e + 1] - r0;
+  const int ne = nl < n ? (int)(nl < 0 ? 0 : nl) : n;
+  const long long cb = col_ptr[e];
+  const long long dl = col_ptr[e + 1] - cb;
+  const int de = dl < dcap ? (int)(dl < 0 ? 0 : dl) : dcap;
+  double* Ab = A + b * (long long)n * n;
+  for (int t = tid; t < dcap * 8; t += VB_THREADS) vbg_img[t] = 0.0;
+  __syncthreads();
+  for (int i0 = 0; i0 < n; i0 += 8) {
+    const bool live = i0 < ne;
+    if (live) {
+      // wave w scatters (pass 0) row i0 + w
+      const int i = i0 + w;
+      if (i < ne) {
+        const double si = sqrt(c[r0 + i]);
+        const long long ka = nip[r0 + i], kb = nip[r0 + i + 1];
+        for (long long k = ka + lane; k < kb; k += 64) {
+          const long long col = pos[k] - cb;
+          if (col >= 0 && col < de) vbg_img[(int)col * 8 + w] = si * val[k];
+        }
+      }
+      __syncthreads();
+    }
+    for (int j = tid; j < n; j += VB_THREADS) {
+      double acc[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+      if (live && j < ne && j <= i0 + 7) {
+        const double sj = sqrt(c[r0 + j]);
+        const long long ka = nip[r0 + j], kb = nip[r0 + j + 1];
+        for (long long k = ka; k < kb; ++k) {
+          const long long col = pos[k] - cb;
+          if (col < 0 || col >= de) continue;
+          const double v = sj * val[k];
+          const double* im = vbg_img + (int)col * 8;
+#pragma unroll
+          for (int s = 0; s < 8; ++s) acc[s] = fma(v, im[s], acc[s]);
+        }
+      }
+#pragma unroll
+      for (int s = 0; s < 8; ++s) {
+        const int i = i0 + s;
+        if (i >= n) continue;
+        double v = 0.0;
+        if (j <= i) v = i < ne ? acc[s] + (i == j ? lam : 0.0) : (i == j ? 1.0 : 0.0);
+        Ab[(long long)i * n + j] = v;
+      }
+    }
+    if (live) {
+      __syncthreads();
+      const int i = i0 + w;
+      if (i < ne) {
+        const long long ka = nip[r0 + i], kb = nip[r0 + i + 1];
+        for (long long k = ka + lane; k < kb; k += 64) {
+          const long long col = pos[k] - cb;
+          if (col >= 0 && col < de) vbg_img[(int)col * 8 + w] = 0.0;
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// Blocked Cholesky of K [B, n, n] in place (n <= VAR_BLOCKED_MMAX), one work-group per problem, left-looking over
+// 16-column panels: the 16 rows L[k0 .. k0+16)[0 .. k0) of the panel sit in LDS (the A operand of every tile of the
+// panel), the rows below come from the factor in global memory, and the products run on the fp64 matrix cores. The
+// diagonal tile's K range is split over the waves and summed in wave order; one wave factors it and inverts the
+// factor, and every other tile is P L11^-T = (L11^-1 P^T)^T by one more MFMA round. Only the lower triangle of K is
+// read. Rows / columns >= nv[b] are the identity; the strict upper triangle of the result is zero. info[b] as
+// batched_chol_kernel (on a bad pivot the kernel stops; every access stays inside the problem's slab).
+__global__ __launch_bounds__(VB_THREADS) void blocked_chol_kernel(int B, int n, const long long* __restrict__ nv,
+                                                                  double* K, int* __restrict__ info) {
+  extern __shared__ double bc_lds[];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int lr = lane & 15, g = lane >> 4;
+  const long long b = blockIdx.x;
+  if (b >= B) return;
+  const long long ml = nv[b];
+  const int m = ml < 0 ? 0 : (ml < n ? (int)ml : n);
+  const int ld = vb_ld(n);
+  double* sB = bc_lds;                        // [16][ld]
+  double* sD = sB + VB_T * ld;                // [16][17]
+  double* sI = sD + VB_T * 17;                // [16][16]
+  double* sP = sI + VB_T * VB_T;              // [VB_WAVES][256] partial diagonal tiles
+  int* sflag = (int*)(sP + VB_WAVES * 256);
+  double* Kb = K + b * (long long)n * n;
+  if (tid == 0) *sflag = 0;
+  __syncthreads();
+  int bad = 0;
+  for (int k0 = 0; k0 < m; k0 += VB_T) {
+    for (int t = tid; t < VB_T * k0; t += VB_THREADS) {
+      const int cc = t / k0, k = t - cc * k0;
+      sB[cc * ld + k] = k0 + cc < m ? Kb[(long long)(k0 + cc) * n + k] : 0.0;
+    }
+    __syncthreads();
+    {
+      // diagonal tile: K steps split over the waves
+      const int steps = k0 / 4;
+      const int s_lo = (int)((long long)steps * w / VB_WAVES), s_hi = (int)((long long)steps * (w + 1) / VB_WAVES);
+      v4d acc = {0.0, 0.0, 0.0, 0.0};
+      for (int s = s_lo; s < s_hi; ++s) {
+        const double a = sB[lr * ld + 4 * s + g];
+        acc = mfma_f64_16x16x4(a, a, acc);
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) sP[w * 256 + q * 64 + lane] = acc[q];
+    }
+    __syncthreads();
+    if (w == 0) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int rr = g + 4 * q, cc = lr;
+        double s = 0.0;
+        for (int ww = 0; ww < VB_WAVES; ++ww) s += sP[ww * 256 + q * 64 + lane];
+        const bool ok = k0 + rr < m && k0 + cc < m;
+        double v = rr == cc ? 1.0 : 0.0;
+        if (ok && cc <= rr) v = Kb[(long long)(k0 + rr) * n + k0 + cc] - s;
+        sD[rr * 17 + cc] = v;
+      }
+      const int wl = m - k0 < VB_T ? m - k0 : VB_T;
+      const int f = vb_chol16(sD, wl, lane);
+      if (f) {
+        if (lane == 0) *sflag = k0 + f;
+      } else {
+        vb_inv16(sD, sI, lane);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int rr = lr, cc = g + 4 * q;
+          if (k0 + rr < m && k0 + cc < m) Kb[(long long)(k0 + rr) * n + k0 + cc] = cc <= rr ? sD[rr * 17 + cc] : 0.0;
+        }
+      }
+    }
+    __syncthreads();
+    bad = *sflag;
+    if (bad) break;
+    const int ntile = (m - k0 + VB_T - 1) / VB_T;
+    for (int t = 1 + w; t < ntile; t += VB_WAVES) {
+      const int row = k0 + VB_T * t + lr;
+      const bool rowok = row < m;
+      double* Lr = Kb + (long long)(rowok ? row : 0) * n;
+      v4d acc = {0.0, 0.0, 0.0, 0.0};
+      for (int kk = 0; kk < k0; kk += VB_T) {      // k0 is a multiple of 16: four loads in flight per round
+        double bq[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) bq[u] = Lr[kk + 4 * u + g];
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+          acc = mfma_f64_16x16x4(sB[lr * ld + kk + 4 * u + g], rowok ? bq[u] : 0.0, acc);
+      }
+      // acc[q] = sum_k L[k0 + c][k] L[row][k], c = g + 4 q: P^T[c][row] = K[row][k0 + c] - acc[q]
+      v4d x = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int cc = g + 4 * q;
+        const double p = (rowok && k0 + cc < m) ? Lr[k0 + cc] - acc[q] : 0.0;
+        x = mfma_f64_16x16x4(sI[lr * VB_T + cc], p, x);
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int cc = g + 4 * q;
+        if (rowok && k0 + cc < m) Lr[k0 + cc] = x[q];
+      }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) info[b] = bad;
+  for (int r = w; r < n; r += VB_WAVES)
+    for (int cc = lane; cc < n; cc += 64) {
+      if (cc > r) Kb[(long long)r * n + cc] = 0.0;
+      else if (r >= m) Kb[(long long)r * n + cc] = r == cc ? 1.0 : 0.0;
+    }
+}
+
+// T = G^-1 in place over the factors L [B, n, n] of blocked_chol_kernel (order nv[b]; padding rows stay the
+// identity): block row i of T is -L_ii^-1 (L[i][0 .. i0) T[0 .. i0)][:]) with T_ii = L_ii^-1 -- the forward
+// substitution of the identity in 16-column panels, which are zero above their first row, so tile (i, j) sums over
+// k in [j0, i0) only. The 16 rows of L sit in LDS (they are overwritten by the result), the solved row blocks of T
+// are read from global memory, the products run on the fp64 matrix cores.
+__global__ __launch_bounds__(VB_THREADS) void blocked_trinv_kernel(int B, int n, const long long* __restrict__ nv,
+                                                                   double* L) {
+  extern __shared__ double bt_lds[];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int lr = lane & 15, g = lane >> 4;
+  const long long b = blockIdx.x;
+  if (b >= B) return;
+  const long long ml = nv[b];
+  const int m = ml < 0 ? 0 : (ml < n ? (int)ml : n);
+  const int ld = vb_ld(n);
+  double* sA = bt_lds;                        // [16][ld]
+  double* sD = sA + VB_T * ld;                // [16][17]
+  double* sI = sD + VB_T * 17;                // [16][16]
+  double* Lb = L + b * (long long)n * n;
+  for (int i0 = 0; i0 < m; i0 += VB_T) {
+    for (int t = tid; t < VB_T * i0; t += VB_THREADS) {
+      const int rr = t / i0, k = t - rr * i0;
+      sA[rr * ld + k] = i0 + rr < m ? Lb[(long long)(i0 + rr) * n + k] : 0.0;
+    }
+    if (tid < VB_T * VB_T) {
+      const int rr = tid >> 4, cc = tid & 15;
+      double v = rr == cc ? 1.0 : 0.0;
+      if (i0 + rr < m && i0 + cc < m) v = cc <= rr ? Lb[(long long)(i0 + rr) * n + i0 + cc] : 0.0;
+      sD[rr * 17 + cc] = v;
+    }
+    __syncthreads();
+    if (w == 0) vb_inv16(sD, sI, lane);
+    __syncthreads();
+    if (tid < VB_T * VB_T) {
+      const int rr = tid >> 4, cc = tid & 15;
+      if (i0 + rr < m && i0 + cc < m) Lb[(long long)(i0 + rr) * n + i0 + cc] = sI[rr * VB_T + cc];
+    }
+    for (int j = w; j < i0 / VB_T; j += VB_WAVES) {
+      const int j0 = VB_T * j;
+      v4d acc = {0.0, 0.0, 0.0, 0.0};
+      for (int kk = j0; kk < i0; kk += VB_T) {     // i0 - j0 is a multiple of 16: four loads in flight per round
+        double bq[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) bq[u] = Lb[(long long)(kk + 4 * u + g) * n + j0 + lr];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc = mfma_f64_16x16x4(sA[lr * ld + kk + 4 * u + g], bq[u], acc);
+      }
+      v4d x = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int q = 0; q < 4; ++q) x = mfma_f64_16x16x4(-sI[lr * VB_T + g + 4 * q], acc[q], x);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int rr = g + 4 * q;
+        if (i0 + rr < m) Lb[(long long)(i0 + rr) * n + j0 + lr] = x[q];
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// Variances from T = G^-1 [B, n, n] (blocked_trinv_kernel; order nv[b]) into out[col_ptr[e] + j].
+// MODE 0 (primal): q_j = sum_{k >= j} T[k][j]^2 for j < min(d_e, nv), one thread per column, rows in order.
+// MODE 1 (row space): q_j = |T b_j|^2, B = diag(s) X_e, out = (1 - q_j) / lam for j < d_e <= dcap. Wave w forms the
+//   rows k = w (mod VB_WAVES) of T B in its own LDS image [dcap] as the combination sum_{i <= k} T[k][i] s_i x_i of
+//   the entity's sparse rows (rows in order, four rows' entries in flight) and adds its squares to per-lane sums q
+//   (lane owns the columns = lane mod 64); the waves' sums are added in wave order at the end.
+template <int MODE>
+__global__ __launch_bounds__(VB_THREADS) void var_blk_colnorm_kernel(int B, int n, int dcap,
+                                                                     const double* __restrict__ T,
+                                                                     const long long* __restrict__ nv,
+                                                                     const long long* __restrict__ ents,
+                                                                     const long long* __restrict__ row_ptr,
+                                                                     const long long* __restrict__ col_ptr,
+                                                                     const long long* __restrict__ nip,
+                                                                     const long long* __restrict__ pos,
+                                                                     const double* __restrict__ val,
+                                                                     const double* __restrict__ c, double lam,
+                                                                     double* __restrict__ out) {
+  extern __shared__ double vbc_lds[];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const long long b = blockIdx.x;
+  if (b >= B) return;
+  const long long e = ents[b];
+  const long long ml = nv[b];
+  const int m = ml < 0 ? 0 : (ml < n ? (int)ml : n);
+  const long long cb = col_ptr[e];
+  const long long dl = col_ptr[e + 1] - cb;
+  const double* Tb = T + b * (long long)n * n;
+  if (MODE == 0) {
+    const int ncols = dl < m ? (int)(dl < 0 ? 0 : dl) : m;
+    for (int j = tid; j < ncols; j += VB_THREADS) {
+      double q = 0.0;
+      for (int k = j; k < m; ++k) {
+        const double t = Tb[(long long)k * n + j];
+        q = fma(t, t, q);
+      }
+      out[cb + j] = q;
+    }
+    return;
+  }
+  const int de = dl < dcap ? (int)(dl < 0 ? 0 : dl) : dcap;
+  double* img = vbc_lds;                          // [VB_WAVES][dcap]
+  double* sr = img + (size_t)VB_WAVES * dcap;     // s_i [n]
+  int* sk = (int*)(sr + n);                       // first entry of row i relative to the entity's first [n + 1]
+  const long long r0 = row_ptr[e];
+  const long long e0 = nip[r0];
+  for (int i = tid; i < m; i += VB_THREADS) sr[i] = sqrt(c[r0 + i]);
+  for (int i = tid; i <= m; i += VB_THREADS) sk[i] = (int)(nip[r0 + i] - e0);
+  for (int t = tid; t < VB_WAVES * dcap; t += VB_THREADS) img[t] = 0.0;
+  __syncthreads();
+  double* im = img + (size_t)w * dcap;
+  double q[VAR_BLOCKED_DMAX / 64];
+#pragma unroll
+  for (int u = 0; u < VAR_BLOCKED_DMAX / 64; ++u) q[u] = 0.0;
+  const int klast = sk[m] - 1;                    // last entry of the entity's rows (< 0: no entries, every q_j = 0)
+  for (int k = w; klast >= 0 && k < m; k += VB_WAVES) {
+    const double* Tk = Tb + (long long)k * n;
+    // rounds of VBC_R rows i; the loads of the next round go out before this round's LDS updates
+    double t[2][VBC_R], v[2][VBC_R];
+    int col[2][VBC_R], ka[2][VBC_R], kb[2][VBC_R];
+#define VBC_LOAD(S, I0)                                              \
+  _Pragma("unroll") for (int u = 0; u < VBC_R; ++u) {                \
+    /* every load is unconditional on a clamped, valid index (no branch between the loads of a round) */ \
+    const bool ok = (I0) + u <= k;                                   \
+    const int ii = ok ? (I0) + u : k;                                \
+    ka[S][u] = sk[ii];                                               \
+    kb[S][u] = ok ? sk[ii + 1] : ka[S][u];                           \
+    t[S][u] = Tk[ii] * sr[ii];                                       \
+    const int kx = ka[S][u] + lane;                                  \
+    const bool has = kx < kb[S][u];                                  \
+    const int kc = kx < klast ? kx : klast;                          \
+    const long long cl = pos[e0 + kc] - cb;                          \
+    col[S][u] = (has && cl >= 0 && cl < de) ? (int)cl : -1;          \
+    v[S][u] = val[e0 + kc];                                          \
+  }
+#define VBC_APPLY(S)                                                                              \
+  _Pragma("unroll") for (int u = 0; u < VBC_R; ++u) {                                             \
+    if (col[S][u] >= 0) im[col[S][u]] = fma(t[S][u], v[S][u], im[col[S][u]]);                     \
+    for (int kx = ka[S][u] + 64 + lane; kx < kb[S][u]; kx += 64) { /* rows of more than 64 entries */ \
+      const long long cl = pos[e0 + kx] - cb;                                                     \
+      if (cl >= 0 && cl < de) im[(int)cl] = fma(t[S][u], val[e0 + kx], im[(int)cl]);              \
+    }                                                                                             \
+    vb_wave_sync();                                                                               \
+  }
+    VBC_LOAD(0, 0)
+    for (int i = 0; i <= k; i += 2 * VBC_R) {
+      if (i + VBC_R <= k) { VBC_LOAD(1, i + VBC_R) }
+      VBC_APPLY(0)
+      if (i + VBC_R <= k) {
+        if (i + 2 * VBC_R <= k) { VBC_LOAD(0, i + 2 * VBC_R) }
+        VBC_APPLY(1)
+      }
+    }
+#undef VBC_LOAD
+#undef VBC_APPLY
+#pragma unroll
+    for (int u = 0; u < VAR_BLOCKED_DMAX / 64; ++u) {
+      const int cc = u * 64 + lane;
+      if (cc < de) {
+        const double y = im[cc];
+        q[u] = fma(y, y, q[u]);
+        im[cc] = 0.0;
+      }
+    }
+    vb_wave_sync();
+  }
+#pragma unroll
+  for (int u = 0; u < VAR_BLOCKED_DMAX / 64; ++u) {
+    const int cc = u * 64 + lane;
+    if (cc < de) im[cc] = q[u];
+  }
+  __syncthreads();
+  for (int j = tid; j < de; j += VB_THREADS) {
+    double s = 0.0;
+    for (int ww = 0; ww < VB_WAVES; ++ww) s += img[(size_t)ww * dcap + j];
+    out[cb + j] = (1.0 - s) / lam;
   }
 }
 
@@ -1539,6 +2098,70 @@ int pml_chol_colnorm(int mode, int B, int n, const double* L, const long long* n
   } else {
     hipLaunchKernelGGL(chol_colnorm_kernel<0>, dim3((unsigned)B), dim3(64), (size_t)lds, (hipStream_t)stream, B, n, L,
                        nv, ents, row_ptr, col_ptr, nip, pos, val, c, lam, out);
+  }
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- blocked FULL-variance route (VAR_MMAX < n <= VAR_BLOCKED_MMAX), one work-group per problem ----
+int pml_var_blocked_mmax() { return VAR_BLOCKED_MMAX; }
+int pml_var_blocked_dmax() { return VAR_BLOCKED_DMAX; }
+
+static_assert(VB_WAVES == 8, "var_blk_gram_kernel scatters one image row per wave");
+
+// A [B, n, n] (lower triangle) for the entities ents[B]: mode 0 primal lam I + X_e^T diag(c) X_e (d_e <= n), mode 1
+// row space lam I + diag(s) X_e X_e^T diag(s) (n_e <= n, d_e <= dcap <= VAR_BLOCKED_DMAX)
+int pml_var_blocked_assemble(int mode, int B, int n, int dcap, const long long* ents, const long long* row_ptr,
+                             const long long* col_ptr, const long long* nip, const long long* pos, const double* val,
+                             const double* c, double lam, double* A, void* stream) {
+  if (B <= 0) return 0;
+  if (n < 1 || n > VAR_BLOCKED_MMAX || (mode != 0 && mode != 1)) return -22;
+  if (mode == 0) {
+    const size_t lds = (size_t)VB_WAVES * (n + (n + 1) / 2) * sizeof(double);
+    hipLaunchKernelGGL(var_blk_normal_kernel, dim3((unsigned)B), dim3(VB_THREADS), lds, (hipStream_t)stream, B, n, ents,
+                       row_ptr, col_ptr, nip, pos, val, c, lam, A);
+  } else {
+    if (dcap < 1 || dcap > VAR_BLOCKED_DMAX) return -22;
+    const size_t lds = (size_t)dcap * 8 * sizeof(double);
+    hipLaunchKernelGGL(var_blk_gram_kernel, dim3((unsigned)B), dim3(VB_THREADS), lds, (hipStream_t)stream, B, n, dcap,
+                       ents, row_ptr, col_ptr, nip, pos, val, c, lam, A);
+  }
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// In-place Cholesky of K [B, n, n] (n <= VAR_BLOCKED_MMAX; lower triangle read); nv / info as pml_batched_chol
+int pml_blocked_chol(int B, int n, const long long* nv, double* K, int* info, void* stream) {
+  if (B <= 0) return 0;
+  if (n < 1 || n > VAR_BLOCKED_MMAX) return -22;
+  const size_t lds = ((size_t)VB_T * vb_ld(n) + VB_T * 17 + VB_T * VB_T + VB_WAVES * 256) * sizeof(double) + 16;
+  if (lds > 160 * 1024) return -22;
+  hipLaunchKernelGGL(blocked_chol_kernel, dim3((unsigned)B), dim3(VB_THREADS), lds, (hipStream_t)stream, B, n, nv, K,
+                     info);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// out[col_ptr[e] + j] from the factors L [B, n, n] of pml_blocked_chol: L becomes G^-1 in place, then mode 0
+// |G^-1 e_j|^2, mode 1 (1 - |G^-1 b_j|^2) / lam (d_e <= dcap <= VAR_BLOCKED_DMAX)
+int pml_var_blocked_colnorm(int mode, int B, int n, int dcap, double* L, const long long* nv, const long long* ents,
+                            const long long* row_ptr, const long long* col_ptr, const long long* nip,
+                            const long long* pos, const double* val, const double* c, double lam, double* out,
+                            void* stream) {
+  if (B <= 0) return 0;
+  if (n < 1 || n > VAR_BLOCKED_MMAX || (mode != 0 && mode != 1)) return -22;
+  if (mode && (!(lam > 0.0) || dcap < 1 || dcap > VAR_BLOCKED_DMAX)) return -22;
+  const size_t lds_t = ((size_t)VB_T * vb_ld(n) + VB_T * 17 + VB_T * VB_T) * sizeof(double);
+  hipLaunchKernelGGL(blocked_trinv_kernel, dim3((unsigned)B), dim3(VB_THREADS), lds_t, (hipStream_t)stream, B, n, nv, L);
+  LAUNCH_CHECK();
+  if (mode) {
+    const size_t lds = ((size_t)VB_WAVES * dcap + n) * sizeof(double) + (size_t)(n + 2) * sizeof(int);
+    if (lds > 160 * 1024) return -22;
+    hipLaunchKernelGGL(var_blk_colnorm_kernel<1>, dim3((unsigned)B), dim3(VB_THREADS), lds, (hipStream_t)stream, B, n,
+                       dcap, L, nv, ents, row_ptr, col_ptr, nip, pos, val, c, lam, out);
+  } else {
+    hipLaunchKernelGGL(var_blk_colnorm_kernel<0>, dim3((unsigned)B), dim3(VB_THREADS), 0, (hipStream_t)stream, B, n, 1,
+                       L, nv, ents, row_ptr, col_ptr, nip, pos, val, c, lam, out);
   }
   LAUNCH_CHECK();
   return 0;

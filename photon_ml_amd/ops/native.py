@@ -801,6 +801,16 @@ def game_lib() -> Optional[ctypes.CDLL]:
         lib.pml_var_scale_gram.restype = c_int
         lib.pml_chol_colnorm.argtypes = [c_int, c_int, c_int] + [c_void_p] * 9 + [c_double, c_void_p, c_void_p]
         lib.pml_chol_colnorm.restype = c_int
+        lib.pml_var_blocked_mmax.argtypes = []
+        lib.pml_var_blocked_mmax.restype = c_int
+        lib.pml_var_blocked_dmax.argtypes = []
+        lib.pml_var_blocked_dmax.restype = c_int
+        lib.pml_var_blocked_assemble.argtypes = [c_int] * 4 + [c_void_p] * 7 + [c_double, c_void_p, c_void_p]
+        lib.pml_var_blocked_assemble.restype = c_int
+        lib.pml_blocked_chol.argtypes = [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]
+        lib.pml_blocked_chol.restype = c_int
+        lib.pml_var_blocked_colnorm.argtypes = [c_int] * 4 + [c_void_p] * 9 + [c_double, c_void_p, c_void_p]
+        lib.pml_var_blocked_colnorm.restype = c_int
         lib.pml_csr_gather_rows.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong,
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         lib.pml_csr_gather_rows.restype = c_int
@@ -1243,6 +1253,8 @@ def rs_primal(ents: torch.Tensor, row_ptr, col_ptr, nip, pos, val, r: torch.Tens
 VAR_MMAX = 128                 # = VAR_MMAX in game_kernels.hip: largest factor order m = min(n_e, d_e) of the HIP path
 VAR_LDS_MAX = 160 * 1024       # LDS of one workgroup
 VAR_PRIMAL, VAR_ROW_SPACE = 0, 1
+VAR_BLOCKED_MMAX = 1024        # = VAR_BLOCKED_MMAX in game_kernels.hip: largest factor order of the blocked route
+VAR_BLOCKED_DMAX = 2048        # = VAR_BLOCKED_DMAX: widest entity of the blocked row-space route (LDS images)
 
 
 def chol_colnorm_lds_bytes(mode: int, n: int) -> int:
@@ -1253,19 +1265,26 @@ def chol_colnorm_lds_bytes(mode: int, n: int) -> int:
 
 def check_var_class(mode: int, n: int, ents: torch.Tensor, row_ptr: torch.Tensor, col_ptr: torch.Tensor,
                     nv: Optional[torch.Tensor] = None, csr=None, c: Optional[torch.Tensor] = None,
-                    out: Optional[torch.Tensor] = None) -> None:
+                    out: Optional[torch.Tensor] = None, blocked: bool = False) -> None:
     """Host-side check of everything the FULL-variance kernels index by, for one size class (``mode``:
     ``VAR_PRIMAL`` / ``VAR_ROW_SPACE``; ``n``: the class's padded order). Raises ValueError instead of launching:
     the class size and its LDS bytes, every ``ents`` value inside the entity range, the members' ``d_e`` (primal) or
     ``n_e`` (row space) and ``nv`` within ``n``, the row / coefficient / entry vectors long enough. One readback.
-    With ``PML_CHECK_KERNEL_INPUTS=1`` also every column of the members' entries inside the entity's range."""
+    With ``PML_CHECK_KERNEL_INPUTS=1`` also every column of the members' entries inside the entity's range.
+    ``blocked``: the class belongs to the blocked route (order in ``(VAR_MMAX, VAR_BLOCKED_MMAX]``, no LDS bound on
+    the order; see :func:`check_var_blocked_class`)."""
     if mode not in (VAR_PRIMAL, VAR_ROW_SPACE):
         raise ValueError(f"FULL variance: unknown mode {mode}")
-    if not 1 <= int(n) <= VAR_MMAX:
-        raise ValueError(f"FULL variance: class order {n} outside [1, {VAR_MMAX}] (larger entities take the torch path)")
-    lds = chol_colnorm_lds_bytes(mode, int(n))
-    if lds > VAR_LDS_MAX:
-        raise ValueError(f"FULL variance: class order {n} needs {lds} B of LDS > {VAR_LDS_MAX}")
+    if blocked:
+        if not VAR_MMAX < int(n) <= VAR_BLOCKED_MMAX:
+            raise ValueError(f"FULL variance: blocked class order {n} outside ({VAR_MMAX}, {VAR_BLOCKED_MMAX}]")
+    else:
+        if not 1 <= int(n) <= VAR_MMAX:
+            raise ValueError(f"FULL variance: class order {n} outside [1, {VAR_MMAX}] (larger entities take the "
+                             f"torch path)")
+        lds = chol_colnorm_lds_bytes(mode, int(n))
+        if lds > VAR_LDS_MAX:
+            raise ValueError(f"FULL variance: class order {n} needs {lds} B of LDS > {VAR_LDS_MAX}")
     nb = int(row_ptr.numel()) - 1
     if col_ptr.numel() != row_ptr.numel() or nb < 0:
         raise ValueError("FULL variance: row_ptr / col_ptr do not describe the same entities")
@@ -1398,6 +1417,122 @@ def chol_colnorm(mode: int, L: torch.Tensor, nv: torch.Tensor, ents: torch.Tenso
     check(lib.pml_chol_colnorm(int(mode), B, n, L.data_ptr(), nv.data_ptr(), ents.data_ptr(), row_ptr.data_ptr(),
                                col_ptr.data_ptr(), p(nip), p(pos), p(val), p(c) if mode == VAR_ROW_SPACE else None,
                                float(lam), out.data_ptr(), stream_handle(L.device)), "chol_colnorm")
+
+
+# ---- blocked FULL-variance route: VAR_MMAX < m <= VAR_BLOCKED_MMAX, matrices in a global workspace ----------------
+def var_blocked_dcap(dmax: int) -> int:
+    """LDS image width of a blocked row-space class whose widest entity has ``dmax`` coefficients (a multiple of 64)."""
+    return max(64, (int(dmax) + 63) // 64 * 64)
+
+
+def check_var_blocked_class(mode: int, n: int, ents: torch.Tensor, row_ptr: torch.Tensor, col_ptr: torch.Tensor,
+                            nv: Optional[torch.Tensor] = None, csr=None, c: Optional[torch.Tensor] = None,
+                            out: Optional[torch.Tensor] = None, work: Optional[torch.Tensor] = None,
+                            dcap: Optional[int] = None) -> None:
+    """Host-side check of everything the blocked FULL-variance kernels index by, for one class or one chunk of it:
+    everything :func:`check_var_class` checks with the class order in ``(VAR_MMAX, VAR_BLOCKED_MMAX]``; the workspace
+    ``work`` (contiguous fp64, at least ``len(ents) * n * n``); in row-space mode every member's ``d_e <= dcap <=
+    VAR_BLOCKED_DMAX``. With ``PML_CHECK_KERNEL_INPUTS=1`` also the canonical CSR of the members' rows: columns inside
+    the entity's range and strictly increasing inside a row. Raises ValueError; nothing is launched."""
+    check_var_class(mode, n, ents, row_ptr, col_ptr, nv, csr, c, out, blocked=True)
+    B = int(ents.numel())
+    if work is not None and (work.dtype != torch.float64 or not work.is_contiguous() or not work.is_cuda
+                             or work.numel() < B * int(n) * int(n)):
+        raise ValueError(f"FULL variance: the blocked workspace must be contiguous fp64 on the device with at least "
+                         f"{B} x {n} x {n} elements")
+    if mode == VAR_ROW_SPACE and B:
+        if dcap is None or not 1 <= int(dcap) <= VAR_BLOCKED_DMAX:
+            raise ValueError(f"FULL variance: blocked row-space image width {dcap} outside [1, {VAR_BLOCKED_DMAX}]")
+        d_hi = int((col_ptr[ents + 1] - col_ptr[ents]).max())
+        if d_hi > int(dcap):
+            raise ValueError(f"FULL variance: a blocked row-space entity has {d_hi} > {dcap} coefficients")
+    if csr is not None and B and os.environ.get("PML_CHECK_KERNEL_INPUTS", "0") == "1":
+        nip, pos, _ = csr
+        n_e = row_ptr[ents + 1] - row_ptr[ents]
+        tot = int(n_e.sum())
+        rows = torch.repeat_interleave(row_ptr[ents] - (torch.cumsum(n_e, 0) - n_e), n_e, output_size=tot)
+        rows = rows + torch.arange(tot, device=ents.device)
+        k0 = nip[rows]
+        nk = nip[rows + 1] - k0
+        nnz = int(nk.sum())
+        idx = torch.repeat_interleave(k0 - (torch.cumsum(nk, 0) - nk), nk, output_size=nnz)
+        idx = idx + torch.arange(nnz, device=ents.device)
+        first = torch.zeros(nnz, dtype=torch.bool, device=ents.device)
+        first[(torch.cumsum(nk, 0) - nk)[nk > 0]] = True
+        p = pos[idx]
+        if nnz > 1 and bool(((p[1:] <= p[:-1]) & ~first[1:]).any()):
+            raise ValueError("FULL variance: the columns inside a row are not strictly increasing (canonical CSR)")
+
+
+def var_blocked_assemble(mode: int, ents: torch.Tensor, n: int, row_ptr: torch.Tensor, col_ptr: torch.Tensor, csr,
+                         c: torch.Tensor, lam: float, work: torch.Tensor, dcap: Optional[int] = None,
+                         validated: bool = False) -> torch.Tensor:
+    """Normal matrices of the blocked route into the workspace: ``A [B, n, n]`` (a view of ``work``) for the entities
+    ``ents`` — ``VAR_PRIMAL``: ``lam I + X_e^T diag(c) X_e`` (``d_e <= n``; ``var_blk_normal_kernel``),
+    ``VAR_ROW_SPACE``: ``lam I + diag(s) X_e X_e^T diag(s)``, ``s = sqrt(c)`` (``n_e <= n``, ``d_e <= dcap``;
+    ``var_blk_gram_kernel``). Only the lower triangle is formed (the strict upper triangle is zero); rows / columns
+    beyond the entity's order are the identity. One work-group per entity; canonical CSR as :func:`var_normal`."""
+    lib = require_game_lib()
+    if not validated:
+        check_var_blocked_class(mode, n, ents, row_ptr, col_ptr, None, csr, c, None, work, dcap)
+    B = int(ents.numel())
+    A = work[:B * n * n].view(B, n, n)
+    if B:
+        nip, pos, val = csr
+        check(lib.pml_var_blocked_assemble(int(mode), B, int(n), int(dcap or 1), ents.data_ptr(), row_ptr.data_ptr(),
+                                           col_ptr.data_ptr(), nip.data_ptr(), pos.data_ptr(), val.data_ptr(),
+                                           c.data_ptr(), float(lam), A.data_ptr(), stream_handle(ents.device)),
+              "var_blocked_assemble")
+    return A
+
+
+def blocked_cholesky(K: torch.Tensor, nv: torch.Tensor):
+    """In-place lower Cholesky factors of the fp64 device batch ``K [B, n, n]``, ``n <= VAR_BLOCKED_MMAX``
+    (``blocked_chol_kernel``: one work-group per problem, the factor in global memory, 16-column panels in LDS, the
+    products on the fp64 matrix cores). Only the lower triangle of ``K`` is read; rows / columns ``>= nv[b]`` are
+    treated as the identity; the strict upper triangle of the result is zero. Returns ``(K, info)`` with ``info`` as
+    :func:`batched_cholesky`."""
+    if K.dim() != 3 or K.shape[1] != K.shape[2] or K.dtype != torch.float64 or not K.is_contiguous() or not K.is_cuda:
+        raise ValueError("blocked_cholesky: K must be a contiguous fp64 [B, n, n] batch on the device")
+    B, n, _ = K.shape
+    if not 1 <= n <= VAR_BLOCKED_MMAX:
+        raise ValueError(f"blocked_cholesky: order {n} outside [1, {VAR_BLOCKED_MMAX}]")
+    if nv.numel() != B:
+        raise ValueError("blocked_cholesky: one factor order per problem")
+    info = torch.zeros(B, dtype=torch.int32, device=K.device)
+    if B:
+        nv = nv.to(K.device, torch.int64).contiguous()
+        check(require_game_lib().pml_blocked_chol(B, n, nv.data_ptr(), K.data_ptr(), info.data_ptr(),
+                                                  stream_handle(K.device)), "blocked_chol")
+    return K, info
+
+
+def var_blocked_colnorm(mode: int, L: torch.Tensor, nv: torch.Tensor, ents: torch.Tensor, row_ptr: torch.Tensor,
+                        col_ptr: torch.Tensor, out: torch.Tensor, lam: float = 0.0, csr=None,
+                        c: Optional[torch.Tensor] = None, dcap: Optional[int] = None,
+                        validated: bool = False) -> None:
+    """Variances from the factors ``L [B, n, n]`` of :func:`blocked_cholesky` into ``out[col_ptr[e] + j]``, as
+    :func:`chol_colnorm` for ``VAR_MMAX < n <= VAR_BLOCKED_MMAX``. ``L`` is overwritten by ``G^-1``
+    (``blocked_trinv_kernel``); ``var_blk_colnorm_kernel`` then takes its squared column norms (``VAR_PRIMAL``) or
+    ``(1 - |G^-1 b_j|^2) / lam`` over the entity's CSR rows (``VAR_ROW_SPACE``; ``d_e <= dcap``)."""
+    lib = require_game_lib()
+    if L.dim() != 3 or L.shape[1] != L.shape[2] or L.dtype != torch.float64 or not L.is_contiguous() \
+            or L.shape[0] != ents.numel():
+        raise ValueError("var_blocked_colnorm: L must be a contiguous fp64 [B, n, n] batch, one per entity")
+    B, n, _ = L.shape
+    if mode == VAR_ROW_SPACE and (csr is None or c is None or not lam > 0):
+        raise ValueError("var_blocked_colnorm: the row-space route needs the CSR, the row curvature and lam > 0")
+    if not validated:
+        check_var_blocked_class(mode, n, ents, row_ptr, col_ptr, nv, csr if mode == VAR_ROW_SPACE else None,
+                                c if mode == VAR_ROW_SPACE else None, out, L, dcap)
+    if not B:
+        return
+    nip, pos, val = csr if mode == VAR_ROW_SPACE else (None, None, None)
+    p = lambda t: None if t is None else t.data_ptr()
+    check(lib.pml_var_blocked_colnorm(int(mode), B, n, int(dcap or 1), L.data_ptr(), nv.data_ptr(), ents.data_ptr(),
+                                      row_ptr.data_ptr(), col_ptr.data_ptr(), p(nip), p(pos), p(val),
+                                      p(c) if mode == VAR_ROW_SPACE else None, float(lam), out.data_ptr(),
+                                      stream_handle(L.device)), "var_blocked_colnorm")
 
 
 def downsample_weights(y: torch.Tensor, w0: torch.Tensor, rate: float, binary: bool, seed: int,

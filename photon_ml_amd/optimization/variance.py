@@ -13,8 +13,9 @@ This module is the DEFINITION in plain fp64 torch, on any device:
 
 Each forms ``H_e`` densely and returns ``diag(H_e^-1)``: Cholesky first, and where ``cholesky_ex`` reports a bad pivot
 ``torch.linalg.pinv`` (the later reference's definition). It is the CPU path of the feature, the yardstick of the GPU
-tests and the GPU path of the entities the HIP kernels do not take (``m = min(n_e, d_e) > 128``, a failed factor),
-batched by size bucket in chunks sized by a memory budget.
+tests and the GPU path of the entities the HIP kernels do not take (``m = min(n_e, d_e) > 1024``, or ``> 128`` with the
+blocked route off; a row-space entity wider than the kernels' LDS images; a failed factor), batched by size bucket in
+chunks sized by a memory budget.
 
 :func:`row_space_full_variance` is the Woodbury form the HIP row-space route implements, written once in torch as a
 second yardstick: with ``B = diag(sqrt c) X_e`` and ``lam I + B B^T = G G^T``, ``var_j = (1 - |G^-1 b_j|^2) / lam``.
@@ -153,6 +154,76 @@ def segmented_full_variance(row_ptr: torch.Tensor, col_ptr: torch.Tensor, csr, c
     return out, int(ents.numel())
 
 
+# Blocked route (VAR_MMAX < m <= VAR_BLOCKED_MMAX): upper bounds of the size classes. The work per entity grows like
+# n^3 and every member of a class is padded to the class's largest member, so neighbouring bounds differ by at most a
+# third (at most 2.4x the work of the smallest member); multiples of 32 keep the 16-wide panels and MFMA tiles full.
+BLOCKED_SIZE_CLASSES = (160, 192, 256, 320, 384, 512, 640, 768, 896, 1024)
+
+# Workspace of the blocked route per chunk of a class: one fp64 [n, n] slab per entity (8 MiB at order 1024). 4 GiB
+# hold 512 slabs of order 1024, two work-groups for each of the 256 compute units of an MI355X.
+DEFAULT_BLOCKED_WORKSPACE_BYTES = 4 << 30
+
+
+def blocked_class_bounds(blocked_mmax: int, mmax: int = 128) -> Tuple[int, ...]:
+    """Increasing upper bounds of the blocked size classes for factor orders in ``(mmax, blocked_mmax]``; empty when
+    the route is off (``blocked_mmax <= mmax``). The last bound is ``blocked_mmax`` itself."""
+    blocked_mmax = int(blocked_mmax)
+    if blocked_mmax <= mmax:
+        return ()
+    bounds = [b for b in BLOCKED_SIZE_CLASSES if mmax < b <= blocked_mmax]
+    if not bounds or bounds[-1] < blocked_mmax:
+        bounds.append(blocked_mmax)
+    return tuple(bounds)
+
+
+def blocked_class_of(m: torch.Tensor, bounds) -> torch.Tensor:
+    """Index of the first class of ``bounds`` that holds each factor order of ``m`` (``len(bounds)`` when none does)."""
+    return torch.searchsorted(torch.tensor(list(bounds), dtype=m.dtype, device=m.device), m)
+
+
+def blocked_route_masks(n_e: torch.Tensor, d_e: torch.Tensor, canonical: bool, mmax: int, blocked_mmax: int,
+                        dmax: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Which entities take the blocked primal and the blocked row-space route: live (rows and coefficients), a
+    canonical CSR, ``mmax < min(n_e, d_e) <= blocked_mmax``; primal when ``d_e <= n_e``, else row space, and there only
+    with ``d_e <= dmax`` (the LDS images of the row-space kernels hold one fp64 per coefficient). Pure tensor
+    arithmetic on any device."""
+    m = torch.minimum(n_e, d_e)
+    ok = (n_e > 0) & (d_e > 0) & (m > mmax) & (m <= blocked_mmax)
+    if not canonical or blocked_mmax <= mmax:
+        ok = torch.zeros_like(ok)
+    return ok & (d_e <= n_e), ok & (n_e < d_e) & (d_e <= dmax)
+
+
+# A blocked launch runs one work-group per entity and a work-group fills a compute unit, so a class with at most this
+# many members (the compute units of an MI355X) lasts as long as its largest member whatever the others' orders are:
+# neighbouring classes are merged while they stay within it (one launch sequence instead of several short-handed ones).
+BLOCKED_MERGE_ENTITIES = 256
+
+
+def blocked_merge_classes(counts, limit: int = BLOCKED_MERGE_ENTITIES):
+    """Groups of neighbouring size classes that share one launch sequence: from the largest class down, a class joins
+    the group above it while the group then holds at most ``limit`` entities. ``counts``: entities per class in
+    increasing class order. Returns the groups as lists of class indices, in increasing order; classes without
+    entities belong to no group."""
+    groups, cur, total = [], [], 0
+    for k in range(len(counts) - 1, -1, -1):
+        if counts[k] == 0:
+            continue
+        if cur and total + counts[k] > limit:
+            groups.append(cur[::-1])
+            cur, total = [], 0
+        cur.append(k)
+        total += counts[k]
+    if cur:
+        groups.append(cur[::-1])
+    return groups[::-1]
+
+
+def blocked_chunk_entities(n: int, workspace_bytes: int) -> int:
+    """Entities per launch of a blocked class of order ``n`` under the workspace budget (at least one)."""
+    return max(1, int(workspace_bytes) // (8 * int(n) * int(n)))
+
+
 class SegmentedFullVariance:
     """FULL variances of a segmented random-effect coordinate on the GPU: the routing of its entities, built once
     per dataset (it depends on the data only), and :meth:`compute` per update.
@@ -163,7 +234,15 @@ class SegmentedFullVariance:
     row-space route (``seg_gram`` -> ``var_scale_gram`` -> ``batched_cholesky`` -> ``chol_colnorm``). The rest (larger
     ``m``, an entity too wide for ``seg_gram``'s LDS image, a failed factor, the shapes measured slower on the HIP path)
     goes to :func:`segmented_full_variance`. Entities without rows get ``1 / l2``. The HIP routes need the canonical
-    CSR (strictly increasing columns inside a row); without it every entity takes the torch path."""
+    CSR (strictly increasing columns inside a row); without it every entity takes the torch path.
+
+    ``blocked_mmax`` (0: off; at most ``VAR_BLOCKED_MMAX``) turns on the blocked route for ``VAR_MMAX < m <=
+    blocked_mmax``: the same two routes with the matrices in a global workspace and one work-group per entity
+    (``var_blocked_assemble`` -> ``blocked_cholesky`` -> ``var_blocked_colnorm``), per size class of
+    ``BLOCKED_SIZE_CLASSES`` (neighbouring classes of few members share a launch sequence:
+    :func:`blocked_merge_classes`) and in chunks of ``blocked_workspace_bytes`` (one fp64 ``[n, n]`` slab per entity).
+    Row-space entities need ``d_e <= VAR_BLOCKED_DMAX`` (2048); wider ones stay on the torch path. The counts then
+    carry ``blocked_primal`` and ``blocked_row_space``."""
 
     # Measured slower on the HIP path than in the batched torch fallback (profiles/full_variance_device.md): the
     # row-space class of 97 .. 112 rows when the entity is narrow too (d_e ~ n_e: 3.6 vs 3.0 us per entity at
@@ -173,8 +252,10 @@ class SegmentedFullVariance:
     ROW_SPACE_TORCH_ROWS = 96
     ROW_SPACE_TORCH_COLS = 128
 
-    def __init__(self, row_ptr: torch.Tensor, col_ptr: torch.Tensor, csr, mmax: Optional[int] = None):
-        from ..ops.native import SEG_GRAM_DMAX, VAR_MMAX, VAR_PRIMAL, VAR_ROW_SPACE, check_var_class
+    def __init__(self, row_ptr: torch.Tensor, col_ptr: torch.Tensor, csr, mmax: Optional[int] = None,
+                 blocked_mmax: int = 0, blocked_workspace_bytes: int = DEFAULT_BLOCKED_WORKSPACE_BYTES):
+        from ..ops.native import (SEG_GRAM_DMAX, VAR_BLOCKED_DMAX, VAR_BLOCKED_MMAX, VAR_MMAX, VAR_PRIMAL,
+                                  VAR_ROW_SPACE, check_var_blocked_class, check_var_class, var_blocked_dcap)
         from .row_space import SIZE_CLASSES, _canonical_csr
         dev = row_ptr.device
         self.row_ptr, self.col_ptr = row_ptr.contiguous(), col_ptr.contiguous()
@@ -212,14 +293,45 @@ class SegmentedFullVariance:
                 n = int(st[0])
                 check_var_class(route, n, e, self.row_ptr, self.col_ptr, nv, self.csr)
                 self.classes.append((route, n, e, nv, int(st[1]), int(st[2])))
-        self.rest = torch.nonzero(live & ~(primal | rsp)).squeeze(1)
+        # blocked route: (route, n, ents, nv, dcap) per size class
+        self.blocked_classes = []
+        self.blocked_workspace_bytes = int(blocked_workspace_bytes)
+        blocked_mmax = min(int(blocked_mmax), VAR_BLOCKED_MMAX)
+        self.blocked = blocked_mmax > VAR_MMAX
+        bprimal, brsp = blocked_route_masks(n_e, d_e, canon is not None, VAR_MMAX, blocked_mmax, VAR_BLOCKED_DMAX)
+        bbounds = blocked_class_bounds(blocked_mmax, VAR_MMAX)
+        for route, mask in ((VAR_PRIMAL, bprimal), (VAR_ROW_SPACE, brsp)):
+            ents = torch.nonzero(mask).squeeze(1)
+            if ents.numel() == 0:
+                continue
+            me = m[ents]
+            cls_of = blocked_class_of(me, bbounds)
+            order = torch.argsort(cls_of, stable=True)
+            ents, me, cls_of = ents[order], me[order], cls_of[order]
+            lo = 0
+            counts = torch.bincount(cls_of, minlength=len(bbounds)).tolist()
+            for group in blocked_merge_classes(counts):
+                cnt = sum(counts[k] for k in group)
+                e, nv = ents[lo:lo + cnt].contiguous(), me[lo:lo + cnt].contiguous()
+                lo += cnt
+                n, dmax = (int(v) for v in torch.stack([nv.max(), d_e[e].max()]).tolist())
+                dcap = var_blocked_dcap(dmax) if route == VAR_ROW_SPACE else None
+                check_var_blocked_class(route, n, e, self.row_ptr, self.col_ptr, nv, self.csr, dcap=dcap)
+                self.blocked_classes.append((route, n, e, nv, dcap))
+        self.rest = torch.nonzero(live & ~(primal | rsp | bprimal | brsp)).squeeze(1)
         self.counts = {"primal": int(primal.sum()), "row_space": int(rsp.sum()),
                        "torch": int(self.rest.numel()), "empty": int(((d_e > 0) & (n_e == 0)).sum())}
+        if self.blocked:
+            self.counts["blocked_primal"] = int(bprimal.sum())
+            self.counts["blocked_row_space"] = int(brsp.sum())
 
-    def compute(self, c: torch.Tensor, l2: float, timings: Optional[list] = None) -> Tuple[torch.Tensor, dict]:
+    def compute(self, c: torch.Tensor, l2: float, timings: Optional[list] = None,
+                workspace_bytes: Optional[int] = None) -> Tuple[torch.Tensor, dict]:
         """Variances packed like ``col_ptr`` for the row curvature ``c`` (fp64 per row) and ``l2 > 0``; and the
         number of entities per route (``torch`` includes the entities whose factor failed). ``timings``: a list that
-        receives ``(route, n, entities, start event, end event)`` per class (benchmarks only)."""
+        receives ``(route, n, entities, start event, end event)`` per class, the blocked classes (``n > VAR_MMAX``)
+        after the others (benchmarks only). ``workspace_bytes``: the blocked route's workspace budget for this call
+        (default: the plan's ``blocked_workspace_bytes``); the chunking does not change any result."""
         from ..ops.native import (VAR_PRIMAL, VAR_ROW_SPACE, batched_cholesky, chol_colnorm, seg_gram, var_normal,
                                   var_scale_gram)
         if not l2 > 0:
@@ -248,6 +360,28 @@ class SegmentedFullVariance:
                 ev1 = torch.cuda.Event(enable_timing=True)
                 ev1.record()
                 timings.append((route, n, int(e.numel()), ev0, ev1))
+        if self.blocked_classes:
+            from ..ops.native import blocked_cholesky, var_blocked_assemble, var_blocked_colnorm
+            budget = self.blocked_workspace_bytes if workspace_bytes is None else int(workspace_bytes)
+            steps = [min(int(e.numel()), blocked_chunk_entities(n, budget)) for _, n, e, _, _ in self.blocked_classes]
+            work = torch.empty(max(s * n * n for s, (_, n, *_) in zip(steps, self.blocked_classes)),
+                               dtype=torch.float64, device=dev)
+            for step, (route, n, e, nv, dcap) in zip(steps, self.blocked_classes):
+                if timings is not None:
+                    ev0 = torch.cuda.Event(enable_timing=True)
+                    ev0.record()
+                rs = route == VAR_ROW_SPACE
+                for a in range(0, int(e.numel()), step):
+                    ec, nvc = e[a:a + step], nv[a:a + step]
+                    A = var_blocked_assemble(route, ec, n, rp, cp, self.csr, c, l2, work, dcap, validated=True)
+                    L, info = blocked_cholesky(A, nvc)
+                    var_blocked_colnorm(route, L, nvc, ec, rp, cp, out, l2, self.csr if rs else None,
+                                        c if rs else None, dcap, validated=True)
+                    failed.append((ec, info))
+                if timings is not None:
+                    ev1 = torch.cuda.Event(enable_timing=True)
+                    ev1.record()
+                    timings.append((route, n, int(e.numel()), ev0, ev1))
         rest = self.rest
         if failed:
             any_bad = torch.stack([(i != 0).any() for _, i in failed]).tolist()      # one readback for all classes

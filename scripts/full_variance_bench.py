@@ -6,7 +6,8 @@ distinct sorted columns and N(0,1) values, curvature of a logistic loss):
 
 * ``wide``   game5pl-like wide entities: 5 .. 64 rows (Pareto 1.3), d_e = 1001 -> the row-space route;
 * ``fused``  the entity sizes of ``scripts/re_fused_bench.py`` (65 .. 20000 rows, Pareto 1.3) with d_e = 1001: rows
-             <= 128 take the row-space route, the rest the torch fallback (m = min(n_e, d_e) > 128);
+             <= 128 take the row-space route, 129 .. 1000 rows the blocked row-space route and more rows the blocked
+             primal route (with ``--no-blocked`` all of m = min(n_e, d_e) > 128 takes the torch fallback);
 * ``tall``   the same sizes with 100-feature pools (d_e = 101 <= n_e) -> the primal route.
 
 For every sample: the FULL variance (all routes, as the coordinate runs it), the same entities through the batched
@@ -15,7 +16,8 @@ per size class the HIP time (device events inside one ``compute``) against the t
 Times are medians over ``--reps`` runs after a warm-up, each ending in a device synchronise; the HIP and torch
 results are compared before anything is timed.
 
-usage: python scripts/full_variance_bench.py [--wide N] [--fused N] [--tall N] [--reps R] [--class-cap N] [--out FILE]
+usage: python scripts/full_variance_bench.py [--wide N] [--fused N] [--tall N] [--reps R] [--class-cap N]
+                                             [--no-blocked] [--out FILE]
 """
 import argparse
 import json
@@ -74,30 +76,32 @@ def timed(fn, reps: int):
     return statistics.median(ts), min(ts)
 
 
-def bench_sample(name: str, n_e: torch.Tensor, pool: int, lam: float, reps: int, class_cap: int, dev) -> dict:
+def bench_sample(name: str, n_e: torch.Tensor, pool: int, lam: float, reps: int, class_cap: int, dev,
+                 blocked: bool = True) -> dict:
     from photon_ml_amd.constants import EPSILON
     from photon_ml_amd.ops.device import DeviceGLMData
-    from photon_ml_amd.ops.native import VAR_PRIMAL
+    from photon_ml_amd.ops.native import VAR_BLOCKED_MMAX, VAR_MMAX, VAR_PRIMAL
     from photon_ml_amd.optimization.variance import SegmentedFullVariance, segmented_full_variance
     row_ptr, col_ptr, csr, c = make_sample(n_e, pool, 1, dev)
     E, N = int(n_e.numel()), int(n_e.sum())
     print(f"[{name}] {E} entities, {N} rows, {N * NNZ / 1e6:.1f}M non-zeros, n_e {int(n_e.min())}..{int(n_e.max())}, "
           f"d_e {pool + 1}", flush=True)
     t0 = time.perf_counter()
-    plan = SegmentedFullVariance(row_ptr, col_ptr, csr)
+    plan = SegmentedFullVariance(row_ptr, col_ptr, csr, blocked_mmax=VAR_BLOCKED_MMAX if blocked else 0)
     torch.cuda.synchronize()
     out = {"sample": name, "entities": E, "rows": N, "d_e": pool + 1, "lambda": lam, "routes": plan.counts,
            "plan_build_ms": (time.perf_counter() - t0) * 1e3}
     var, stats = plan.compute(c, lam)
     out["routes"] = stats
     # correctness first: the HIP routes against the torch definition on (a sample of) their entities
-    hip_ents = torch.cat([e for _, _, e, *_ in plan.classes]) if plan.classes else torch.zeros(0, dtype=torch.int64,
-                                                                                                device=dev)
-    chk = hip_ents[torch.linspace(0, max(hip_ents.numel() - 1, 0), min(hip_ents.numel(), 256), device=dev).long()]
-    if chk.numel():
-        ref, _ = segmented_full_variance(row_ptr, col_ptr, csr, c, lam, ents=chk)
-        m = ref != 0
-        out["max_rel_err_vs_torch"] = float(((var[m] - ref[m]).abs() / ref[m].abs()).max())
+    # (the LDS-resident classes and the blocked classes each on up to 256 of their entities)
+    for key, cls in (("max_rel_err_vs_torch", plan.classes), ("blocked_max_rel_err_vs_torch", plan.blocked_classes)):
+        hip_ents = torch.cat([e for _, _, e, *_ in cls]) if cls else torch.zeros(0, dtype=torch.int64, device=dev)
+        chk = hip_ents[torch.linspace(0, max(hip_ents.numel() - 1, 0), min(hip_ents.numel(), 256), device=dev).long()]
+        if chk.numel():
+            ref, _ = segmented_full_variance(row_ptr, col_ptr, csr, c, lam, ents=chk)
+            m = ref != 0
+            out[key] = float(((var[m] - ref[m]).abs() / ref[m].abs()).max())
     out["full_ms"], out["full_min_ms"] = timed(lambda: plan.compute(c, lam), reps)
     # per class: HIP (events inside one compute; median over reps) vs torch on the same entities (capped)
     per = {}
@@ -108,11 +112,12 @@ def bench_sample(name: str, n_e: torch.Tensor, pool: int, lam: float, reps: int,
         for route, n, b, e0, e1 in tm:
             per.setdefault((route, n, b), []).append(e0.elapsed_time(e1))
     classes = []
-    for (route, n, e, nv, dmax, maxnnz) in plan.classes:
+    for (route, n, e, *_) in plan.classes + plan.blocked_classes:
         hip_ms = statistics.median(per[(route, n, int(e.numel()))])
         sub = e[:class_cap]
         t_ms, _ = timed(lambda: segmented_full_variance(row_ptr, col_ptr, csr, c, lam, ents=sub), max(1, reps // 2))
-        classes.append({"route": "primal" if route == VAR_PRIMAL else "row_space", "n": n, "entities": int(e.numel()),
+        label = ("blocked_" if n > VAR_MMAX else "") + ("primal" if route == VAR_PRIMAL else "row_space")
+        classes.append({"route": label, "n": n, "entities": int(e.numel()),
                         "hip_ms": hip_ms, "hip_us_per_entity": 1e3 * hip_ms / e.numel(),
                         "torch_entities": int(sub.numel()), "torch_ms": t_ms,
                         "torch_us_per_entity": 1e3 * t_ms / sub.numel()})
@@ -143,6 +148,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--class-cap", type=int, default=512, help="entities per class timed through the torch fallback")
     ap.add_argument("--lam", type=float, default=1.0)
+    ap.add_argument("--no-blocked", action="store_true",
+                    help="leave the blocked route (128 < m <= 1024) off: those entities take the torch fallback")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -150,13 +157,14 @@ def main():
     dev = torch.device("cuda")
     res = []
     if a.wide:
-        res.append(bench_sample("wide", pareto_sizes(a.wide, 5.0, 64, 2, dev), 1000, a.lam, a.reps, a.class_cap, dev))
+        res.append(bench_sample("wide", pareto_sizes(a.wide, 5.0, 64, 2, dev), 1000, a.lam, a.reps, a.class_cap, dev,
+                                not a.no_blocked))
     if a.fused:
         res.append(bench_sample("fused", pareto_sizes(a.fused, 65.0, 20000, 1, dev), 1000, a.lam, a.reps,
-                                a.class_cap, dev))
+                                a.class_cap, dev, not a.no_blocked))
     if a.tall:
         res.append(bench_sample("tall", pareto_sizes(a.tall, 65.0, 20000, 1, dev), 100, a.lam, a.reps, a.class_cap,
-                                dev))
+                                dev, not a.no_blocked))
     print(json.dumps(res))
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
