@@ -92,6 +92,10 @@ RS_SMALL_N = int(os.environ.get("PML_RS_SMALL_N", "12"))
 # scripts/gpu_r5_s10.sh): the classes then also compete with each other for the CUs the primal launch leaves
 RS_STREAMS = max(1, int(os.environ.get("PML_RS_STREAMS", "1")))
 RS_BIG_NNZ_RATIO = float(os.environ.get("PML_RS_BIG_NNZ_RATIO", "0.6"))   # n > 64: mean row nnz >= ratio x n
+# smallest Cholesky pivot, relative to its diagonal entry of K_e, of an entity solved in its row space: below it the
+# entity's rows count as linearly dependent and the entity goes to the primal path (rounding through L^-1 grows
+# like eps / sqrt(pivot ratio): 1e-12 at this bound)
+RS_PIVOT_RTOL = 1e-8
 
 
 class _SizeClass:
@@ -112,9 +116,10 @@ class _SizeClass:
 
 class RowSpaceBatch:
     """Entities of a :class:`SegmentedGLMData` with 0 < n_e <= min(nmax, d_e) and a positive-definite Gram
-    matrix, as dense padded batches per size class (:data:`SIZE_CLASSES`). Row-space coefficients of all
-    classes are packed into one flat vector (class after class, ``[B_c, n_c]`` row-major each); ``ents``,
-    ``valid`` and the solver results follow the same order."""
+    matrix (every Cholesky pivot above :data:`RS_PIVOT_RTOL` times its diagonal entry), as dense padded batches
+    per size class (:data:`SIZE_CLASSES`). Row-space coefficients of all classes are packed into one flat vector
+    (class after class, ``[B_c, n_c]`` row-major each); ``ents``, ``valid`` and the solver results follow the same
+    order."""
 
     def __init__(self, seg, nmax: int = 64, csr=None):
         nmax = min(int(nmax), ROW_SPACE_NMAX)
@@ -223,17 +228,22 @@ class RowSpaceBatch:
         # factors: one batched Cholesky launch per class (padding slots = identity); the pivots of every class are
         # checked with ONE readback, and only a class with a failed factor pays a boolean selection
         from ..ops.native import batched_cholesky
-        infos = []
+        # A factor also counts as failed when a pivot is positive only by rounding: for linearly dependent rows
+        # (e.g. a duplicated row) the exact pivot is 0 and the computed one +-eps K_jj, so about every second such
+        # entity would pass the sign test with l_jj ~ 1e-8 |x_j| and L^-T (back-map, foreign warm starts) would
+        # amplify rounding by 1 / l_jj. The pivot relative to its diagonal entry, d_jj / K_jj = l_jj^2 / |L_j|^2
+        # (the squared sine of the angle between row j and the rows before it), must exceed RS_PIVOT_RTOL.
+        oks = []
         for gi, (e, n, valid, rows, K, ne, st) in enumerate(geo):
             with trace_range(f"row-space: Cholesky n={n}"):
-                _, info = batched_cholesky(K, ne)
-            infos.append(info)
-        all_ok = torch.stack([(i == 0).all() for i in infos]).tolist() if infos else []
+                _, info = batched_cholesky(K, ne)                      # K now holds the factor
+                sine = K.diagonal(dim1=1, dim2=2) / torch.linalg.vector_norm(K, dim=2)       # NaN: a zero row
+                oks.append((info == 0) & (sine.amin(1) > RS_PIVOT_RTOL ** 0.5))
+        all_ok = torch.stack([ok.all() for ok in oks]).tolist() if oks else []
         off = 0
         kept = []
-        for (e, n, valid, rows, L, ne, st), info, good in zip(geo, infos, all_ok):
+        for (e, n, valid, rows, L, ne, st), ok, good in zip(geo, oks, all_ok):
             if not good:
-                ok = info == 0
                 if not bool(ok.any()):
                     continue
                 L, rows, valid, e = L[ok].contiguous(), rows[ok], valid[ok], e[ok]

@@ -62,6 +62,69 @@ def make_entities(sizes, d_pool, nnz_row, seed, dense_pool=False, loss="LOGISTIC
     return GameData(y, {"user": x}, {"userId": np.array(ids)}, offsets=0.3 * np.sin(np.arange(r)), weights=w)
 
 
+def make_ragged_entities(spec, seed, loss="LOGISTIC", weighted=True, duplicate_rows=None):
+    """One random-effect shard of ragged rows. ``spec``: per entity ``(n_rows, d_e, row_lengths)``; row i of the
+    entity holds ``min(row_lengths[i % len(row_lengths)], d_e)`` distinct columns of the entity's own block of ``d_e``
+    global columns, and every one of the ``d_e`` columns occurs in some row (the projected width is exactly ``d_e``;
+    ValueError when the rows are too short for that). The columns are spread deterministically first -- the rows take
+    consecutive runs of the block until it is covered -- and the rest is drawn at random. There is NO intercept
+    column: a row of length 0 has no entry at all (it adds a loss term through its offset only), and an entity
+    with ``d_e = 0`` has none in any row.
+
+    Values are normal; the per-entity ground truth is scaled by ``1 / sqrt(max(1, max_len / 16))`` (``max_len``: the
+    entity's longest row), so Poisson margins stay inside the clip as in :func:`make_entities`. Weights and base
+    offsets as there: ``integers(1, 17) / 4`` with about 15 % of the rows at exactly 0.0 (``weighted=False``: all
+    1.0), offsets ``0.3 sin(arange(n))``.
+
+    ``duplicate_rows``: ``{entity index: ((row, earlier row), ...)}`` -- the row becomes a copy (columns and values)
+    of that earlier row of the same entity, which makes the entity's Gram matrix singular."""
+    rng = np.random.default_rng(seed)
+    duplicate_rows = duplicate_rows or {}
+    indptr, cols, vals, ids, z = [0], [], [], [], []
+    base = 0
+    for k, (n, d, lengths) in enumerate(spec):
+        lens = [min(int(lengths[i % len(lengths)]), d) for i in range(n)]
+        wt = rng.normal(size=d) * 0.5 / np.sqrt(max(1.0, max(lens, default=0) / 16.0))
+        dup = {int(i): int(j) for i, j in duplicate_rows.get(k, ())}
+        mine, cursor = [], 0
+        for i, ln in enumerate(lens):
+            if i in dup:
+                assert dup[i] < i, (k, i, dup[i])
+                f, v = mine[dup[i]]
+            else:
+                first = np.arange(cursor, min(cursor + ln, d))
+                cursor += first.size
+                more = rng.choice(np.setdiff1d(np.arange(d), first), size=ln - first.size, replace=False)
+                f = np.sort(np.concatenate([first, more])).astype(np.int64)
+                v = rng.normal(size=ln)
+            mine.append((f, v))
+            cols.append(base + f)
+            vals.append(v)
+            indptr.append(indptr[-1] + f.size)
+            z.append(float(v @ wt[f]) + 0.2 * np.sin(k))
+            ids.append(k)
+        if cursor < d:
+            raise ValueError(f"entity {k}: rows of {sum(lens)} entries cannot cover {d} columns")
+        base += d
+    r = len(ids)
+    x = sp.csr_matrix((np.concatenate(vals) if vals else np.zeros(0), np.concatenate(cols) if cols else
+                       np.zeros(0, np.int64), np.array(indptr)), shape=(r, max(base, 1)))
+    z = np.array(z)
+    if loss == "LOGISTIC":
+        y = (rng.random(r) < 1 / (1 + np.exp(-z))).astype(float)
+    elif loss == "POISSON":
+        y = rng.poisson(np.exp(np.clip(z, -3, 2))).astype(float)
+    elif loss == "SQUARED":
+        y = z + 0.3 * rng.normal(size=r)
+    else:
+        raise ValueError(loss)
+    w = rng.integers(1, 17, size=r) / 4.0
+    w[rng.random(r) < 0.15] = 0.0
+    if not weighted:
+        w = np.ones(r)
+    return GameData(y, {"user": x}, {"userId": np.array(ids)}, offsets=0.3 * np.sin(np.arange(r)), weights=w)
+
+
 def entity_problems(data, partial=None, rows=None, mult=None, perm_seed=None):
     """Per entity, its problem as the oracle sees it: ``(entity id, global feature ids, TorchGLMData in float64 on the
     CPU)`` over the entity's rows (of ``rows`` only, when given) restricted to the features those rows hold (the
