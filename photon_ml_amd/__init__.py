@@ -10,7 +10,7 @@ Layout (see SURVEY.md §1 for the reference layer map):
   models/         GLM model classes, coefficients, fixed/random-effect models, GameModel
   algorithm/      GAME coordinates and coordinate descent
   estimators/     GameEstimator / GameTransformer / GLM lambda-path training
-  evaluation/     evaluators (AUC, RMSE, losses, per-group AUC / precision@k)
+  evaluation/     evaluators (AUC, AUPR, RMSE, losses, per-group AUC / AUPR / precision@k)
   sampling/       down-samplers
   projector/      random-effect projectors (index map, random Gaussian, identity)
   parallel/       torch.distributed (RCCL over xGMI) process groups, sharding, all-to-all routing

@@ -276,9 +276,9 @@ class GameEstimator:
 
     def _validation_evaluators(self, validation: GameData):
         names = self.validation_evaluators or [default_validation_evaluator(self.training_task)]
-        # per-group metrics (AUC:tag, PRECISION@k:tag) live on the training device: their kernels read the scores
-        # where score_rows_kernel wrote them; the simple evaluators keep their placement, except plain AUC under a
-        # process group on a GPU: its bucket exchange and count kernels run where the scores are
+        # per-group metrics (AUC:tag, AUPR:tag, PRECISION@k:tag) live on the training device: their kernels read the
+        # scores where score_rows_kernel wrote them; the simple evaluators keep their placement, except plain AUC /
+        # AUPR under a process group on a GPU: their bucket exchange and counts run where the scores are
         dev = self.device if self.device is not None else default_device()
         types = [parse_evaluator_type(n) for n in names]
         return [build_evaluator(t, validation.response, validation.offsets, validation.weights, validation.id_tags,
@@ -333,10 +333,12 @@ class GameEstimator:
 
 def _evaluates_on(etype, device) -> bool:
     """Whether the evaluator ``etype`` is built on the scoring ``device``: the per-group metrics always, plain AUC
-    under a process group with a GPU device (single-process placement of the simple evaluators is unchanged)."""
+    and AUPR under a process group with a GPU device (single-process placement of the simple evaluators is
+    unchanged)."""
     if etype.is_multi:
         return True
-    return (etype.name == "AUC" and device is not None and torch.device(device).type == "cuda" and is_dist())
+    return (etype.name in ("AUC", "AUPR") and device is not None and torch.device(device).type == "cuda"
+            and is_dist())
 
 
 class GameTransformer:
@@ -351,8 +353,8 @@ class GameTransformer:
         return self._evaluate(data, self.model.score(data, self.device), self.device)
 
     def _evaluate(self, data: GameData, scores, multi_device=None):
-        """``multi_device``: where the per-group evaluators (and, under a process group on a GPU, plain AUC) live
-        (None: with the labels, on the host)."""
+        """``multi_device``: where the per-group evaluators (and, under a process group on a GPU, plain AUC / AUPR)
+        live (None: with the labels, on the host)."""
         evals = None
         if self.validation_evaluators:
             evals = []

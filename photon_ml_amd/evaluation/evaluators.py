@@ -5,23 +5,30 @@ Reference: ``photon-lib/.../evaluation/{Evaluator,EvaluatorType}.scala`` (evalua
 ``photon-api/.../evaluation/*.scala``:
   * AUC (global; MLlib BinaryClassificationMetrics -> UNWEIGHTED, Appendix C.5) ``AreaUnderROCCurveEvaluator``
   * local weighted AUC with tie groups ``AreaUnderROCCurveLocalEvaluator.scala:33-70``
+  * AUPR: area under the precision/recall curve, the trapezoid of ``photon-diagnostics/.../Evaluation.scala:84``
+    (MLlib ``areaUnderPR``, ``diagnostics/evaluation.py::binary_metrics``) as an evaluator: global and UNWEIGHTED
+    like AUC, weighted per group (:func:`aupr_weighted`)
   * RMSE = sqrt(sum w (z-y)^2/2 / N) — the reference's definition, kept for parity (Appendix C.1)
   * logistic / poisson / squared / smoothed-hinge loss sums
-  * multi-evaluators grouped by an id tag: AUC:tag and PRECISION@k:tag, mean over groups with finite values
+  * multi-evaluators grouped by an id tag: AUC:tag, AUPR:tag and PRECISION@k:tag, mean over groups with finite values
     (``MultiEvaluator.scala:49-64``, ``PrecisionAtKLocalEvaluator.scala:39-51``)
-  * name parsing ``AUC``, ``RMSE``, ``LOGISTIC_LOSS``, ..., ``PRECISION@5:queryId``, ``AUC:userId``.
+  * name parsing ``AUC``, ``RMSE``, ``LOGISTIC_LOSS``, ..., ``PRECISION@5:queryId``, ``AUC:userId``, ``AUPR``,
+    ``AUPR:userId``.
 
 Sorting-based metrics run on the device (torch sort / segmented reductions), so the whole validation pass stays
 in HBM; the per-group metrics of a GPU run are HIP kernels over a group layout built once (``segmented.py``).
 
 Under a process group no metric gathers rows:
-  * ``AUC:tag`` / ``PRECISION@k:tag`` route every row once to the rank that owns its group
+  * ``AUC:tag`` / ``AUPR:tag`` / ``PRECISION@k:tag`` route every row once to the rank that owns its group
     (``parallel/sharding.py``: ``entity_keys`` -> ``EntityPartitioner`` -> ``RowRouter``), an evaluation routes the
     scores (one all-to-all of 8 B per row, device to device under RCCL), evaluates the owned groups locally and
     all-reduces (sum, count) of the finite values (SURVEY C18);
   * plain ``AUC`` is :func:`auc_distributed`: local sort, regular sampling, one all-to-all of score
     buckets, integer counts per bucket (``ops/native.py::auc_counts``), a three-integer all-gather. Only when a
-    score is NaN do all ranks take the old gather path together.
+    score is NaN do all ranks take the old gather path together;
+  * plain ``AUPR`` is :func:`aupr_distributed`: the same bucket exchange, then integer class counts per bucket (one
+    small all-gather), every rank's own tie-group terms from int64 cumulative counts, and the partial sums added in
+    rank order on every rank.
 """
 from __future__ import annotations
 
@@ -65,6 +72,56 @@ def auc_weighted(scores: torch.Tensor, labels: torch.Tensor, weights: Optional[t
     return float(raw / (tp * tn))
 
 
+def aupr_weighted(scores: torch.Tensor, labels: torch.Tensor, weights: Optional[torch.Tensor] = None) -> float:
+    """Weighted area under the precision/recall curve, vectorised, on the device of ``scores``.
+
+    Rows sorted by score descending form tie groups g = 1..G (``==``); with ``gp_g`` / ``gn_g`` the group's positive
+    / negative weight and ``TP_g`` / ``FP_g`` their inclusive prefix sums,
+
+        AUPR = (1 / TP_G) sum over groups with gp_g > 0 of gp_g (p_g + q_g) / 2,
+        p_g = TP_g / (TP_g + FP_g),   q_g = TP_{g-1} / (TP_{g-1} + FP_{g-1}) if that denominator is > 0 else p_g,
+
+    NaN without rows or when a class has no weight. With unit weights this is the trapezoid of
+    ``diagnostics/evaluation.py::binary_metrics`` (points (R_g, p_g), first point (0, p_1)). The prefixes before a
+    group are the inclusive prefixes SHIFTED by one group, never inclusive prefix minus the group's sums (that
+    difference cancels when weights span many orders of magnitude). A group without positive weight makes no recall
+    step and adds nothing, and rows of weight 0 never change the value."""
+    s = _t(scores)
+    y = _t(labels, s.device)
+    w = torch.ones_like(s) if weights is None else _t(weights, s.device)
+    if s.numel() == 0:
+        return float("nan")
+    order = torch.argsort(s, descending=True, stable=True)
+    s, y, w = s[order], y[order], w[order]
+    pos = torch.where(y > POSITIVE_RESPONSE_THRESHOLD, w, torch.zeros_like(w))
+    neg = w - pos
+    new_group = torch.ones_like(s, dtype=torch.bool)
+    new_group[1:] = s[1:] != s[:-1]
+    gid = torch.cumsum(new_group.to(torch.int64), 0) - 1
+    ng = int(gid[-1].item()) + 1
+    gp = torch.zeros(ng, dtype=torch.float64, device=s.device).index_add_(0, gid, pos)
+    gn = torch.zeros(ng, dtype=torch.float64, device=s.device).index_add_(0, gid, neg)
+    return _aupr_of_groups(gp, gn, torch.cumsum(gp, 0), torch.cumsum(gn, 0))
+
+
+def _aupr_terms(gp, tp, fp, tp_before, fp_before) -> torch.Tensor:
+    """Sum of ``gp (p + q) / 2`` over the tie groups with ``gp > 0`` (all arguments fp64, one entry per group)."""
+    keep = gp > 0
+    gp, tp, fp, tp_before, fp_before = gp[keep], tp[keep], fp[keep], tp_before[keep], fp_before[keep]
+    p = tp / (tp + fp)
+    den = tp_before + fp_before
+    q = torch.where(den > 0, tp_before / torch.where(den > 0, den, torch.ones_like(den)), p)
+    return torch.sum(gp * (p + q) / 2.0)
+
+
+def _aupr_of_groups(gp, gn, tp, fp) -> float:
+    P, N = float(tp[-1]), float(fp[-1])
+    if not (P > 0 and N > 0):
+        return float("nan")
+    zero = torch.zeros(1, dtype=torch.float64, device=gp.device)
+    return float(_aupr_terms(gp, tp, fp, torch.cat([zero, tp[:-1]]), torch.cat([zero, fp[:-1]])) / tp[-1])
+
+
 def precision_at_k(scores, labels, k: int) -> float:
     s = _t(scores)
     y = _t(labels, s.device)
@@ -92,6 +149,11 @@ def _gather(t: torch.Tensor) -> torch.Tensor:
     return torch.cat([x.to(t.device) for x in all_gather_varlen(t.detach().cpu())])
 
 
+def _rank() -> int:
+    from ..parallel.dist import rank
+    return rank()
+
+
 AUC_SAMPLES = 64      # regular samples per rank that place the score-bucket splitters of auc_distributed
 
 
@@ -107,24 +169,12 @@ def _gather_fixed(t: torch.Tensor) -> torch.Tensor:
     return torch.stack(outs).cpu()
 
 
-def auc_distributed(scores: torch.Tensor, flags: torch.Tensor, info: Optional[dict] = None) -> float:
-    """Exact unweighted AUC of the rows of ALL ranks without gathering them (SURVEY C17); every rank passes its
-    shard's ``scores`` (fp64) and positive ``flags`` (uint8) and gets the same value, bitwise the value
-    ``auc_weighted`` gives on the concatenated rows while ``P N < 2^53``.
-
-    1. ``scores + 0.0`` (so -0.0 ties with 0.0 in the radix sort), sorted descending locally.
-    2. ``AUC_SAMPLES`` regular samples per rank and a NaN flag, one small all-gather; the sorted samples give
-       ``world - 1`` splitters. If any rank saw a NaN, every rank takes the gather path (``auc_weighted`` on all
-       rows): a collective decision.
-    3. The bucket of a row is the number of splitters strictly greater than its score -- a function of the value, so
-       a tie group never straddles ranks; buckets are contiguous in the sorted shard. One all-to-all each for the
-       scores and the flags (``RowRouter.exchange``).
-    4. The receiver sorts its bucket (segments of several ranks) and counts ``(2 raw, P, N)`` as integers (``auc_counts``: HIP on a GPU).
-    5. The three integers of every rank are all-gathered and combined in Python ints: bucket b adds
-       ``2 raw_b + 2 P_before_b N_b`` (``P_before_b``: positives of the higher-score buckets).
-
-    ``info`` (optional dict) receives ``path`` ("buckets" / "gather") and ``bucket_rows`` (rows received here)."""
-    from ..ops.native import auc_counts
+def _score_buckets(scores: torch.Tensor, flags: torch.Tensor, info: Optional[dict]):
+    """Steps 1 to 3 of :func:`auc_distributed`, shared by the bucketed global metrics: local sort, regular samples
+    and the collective NaN decision, one all-to-all of score buckets. Returns ``(path, scores, flags)``:
+    ``"buckets"`` with the received bucket sorted descending (bucket 0, on rank 0, holds the highest scores; a tie
+    group never straddles ranks), ``"gather"`` with this rank's rows in row order when some rank saw a NaN (every
+    rank gets the same answer), ``"empty"`` when no rank holds a row. Fills ``info`` (``path``, ``bucket_rows``)."""
     from ..parallel.dist import world_size
     from ..parallel.sharding import RowRouter
     P = world_size()
@@ -148,10 +198,10 @@ def auc_distributed(scores: torch.Tensor, flags: torch.Tensor, info: Optional[di
     if np.any(got[:, 1] != 0.0):
         if info is not None:
             info["path"] = "gather"
-        return auc_weighted(_gather(s0), _gather(f0.to(torch.float64)), None)
+        return "gather", s0, f0
     samples = np.sort(got[got[:, 0] != 0.0, 2:].ravel())[::-1]
     if samples.size == 0:                                  # no rank holds a row
-        return float("nan")
+        return "empty", None, None
     split = torch.from_numpy(np.ascontiguousarray(samples[[k * samples.size // P for k in range(1, P)]])).to(dev)
     # rows of bucket <= k: those with score >= split[k] (the shard is descending: search its negation)
     ends = torch.searchsorted(-s, -split, right=True).tolist()
@@ -163,6 +213,33 @@ def auc_distributed(scores: torch.Tensor, flags: torch.Tensor, info: Optional[di
     if sum(1 for c in router.recv_counts if c) > 1:         # segments of several ranks: merge them by a sort
         rs, o = torch.sort(rs, descending=True)
         rf = rf[o]
+    return "buckets", rs, rf
+
+
+def auc_distributed(scores: torch.Tensor, flags: torch.Tensor, info: Optional[dict] = None) -> float:
+    """Exact unweighted AUC of the rows of ALL ranks without gathering them (SURVEY C17); every rank passes its
+    shard's ``scores`` (fp64) and positive ``flags`` (uint8) and gets the same value, bitwise the value
+    ``auc_weighted`` gives on the concatenated rows while ``P N < 2^53``.
+
+    1. ``scores + 0.0`` (so -0.0 ties with 0.0 in the radix sort), sorted descending locally.
+    2. ``AUC_SAMPLES`` regular samples per rank and a NaN flag, one small all-gather; the sorted samples give
+       ``world - 1`` splitters. If any rank saw a NaN, every rank takes the gather path (``auc_weighted`` on all
+       rows): a collective decision.
+    3. The bucket of a row is the number of splitters strictly greater than its score -- a function of the value, so
+       a tie group never straddles ranks; buckets are contiguous in the sorted shard. One all-to-all each for the
+       scores and the flags (``RowRouter.exchange``).
+    4. The receiver sorts its bucket (segments of several ranks) and counts ``(2 raw, P, N)`` as integers (``auc_counts``: HIP on a GPU).
+    5. The three integers of every rank are all-gathered and combined in Python ints: bucket b adds
+       ``2 raw_b + 2 P_before_b N_b`` (``P_before_b``: positives of the higher-score buckets).
+
+    Steps 1 to 3 are :func:`_score_buckets`. ``info`` (optional dict) receives ``path`` ("buckets" / "gather") and
+    ``bucket_rows`` (rows received here)."""
+    from ..ops.native import auc_counts
+    path, rs, rf = _score_buckets(scores, flags, info)
+    if path == "gather":
+        return auc_weighted(_gather(rs), _gather(rf.to(torch.float64)), None)
+    if path == "empty":
+        return float("nan")
     counts = auc_counts(rs.contiguous(), rf.contiguous())
     allc = _gather_fixed(counts).tolist()
     tot2 = tp = tn = 0
@@ -175,6 +252,50 @@ def auc_distributed(scores: torch.Tensor, flags: torch.Tensor, info: Optional[di
     if tp == 0 or tn == 0:
         return float("nan")
     return (tot2 / 2.0) / (float(tp) * float(tn))
+
+
+def aupr_distributed(scores: torch.Tensor, flags: torch.Tensor, info: Optional[dict] = None) -> float:
+    """Unweighted AUPR (:func:`aupr_weighted` with unit weights) of the rows of ALL ranks without gathering them;
+    every rank passes its shard's ``scores`` (fp64) and positive ``flags`` (uint8) and gets the same bits.
+
+    The score buckets are those of :func:`auc_distributed` (:func:`_score_buckets`; a NaN on any rank sends every
+    rank down the gather path). Then every rank counts the positives and negatives of its bucket as integers, one
+    small all-gather makes the counts of the higher-score buckets and the totals known exactly, and the rank sums
+    the terms of its own tie groups with torch ops where the bucket lives: ``TP_g`` / ``FP_g`` are int64 cumulative
+    counts plus the counts before the bucket, converted to fp64 (exact below 2^53 rows), the prefixes before a group
+    are those of the group above it. The partial sums are all-gathered and added in rank order on every rank."""
+    path, rs, rf = _score_buckets(scores, flags, info)
+    if path == "gather":
+        return aupr_weighted(_gather(rs), _gather(rf.to(torch.float64)), None)
+    if path == "empty":
+        return float("nan")
+    dev = rs.device
+    nb = int(rs.numel())
+    c = torch.cumsum(rf.to(torch.int64), 0)                  # positives through every row of the bucket
+    pb = int(c[-1]) if nb else 0
+    allc = _gather_fixed(torch.tensor([pb, nb - pb], dtype=torch.int64)).tolist()
+    me = _rank()
+    p_before = sum(int(r[0]) for r in allc[:me])
+    n_before = sum(int(r[1]) for r in allc[:me])
+    P, N = sum(int(r[0]) for r in allc), sum(int(r[1]) for r in allc)
+    part = torch.zeros(1, dtype=torch.float64, device=dev)
+    if nb:
+        last = torch.ones(nb, dtype=torch.bool, device=dev)
+        last[:-1] = rs[1:] != rs[:-1]
+        ends = torch.nonzero(last).flatten()                 # closing row of every tie group
+        tp_i = c[ends] + p_before
+        fp_i = ends + 1 - c[ends] + n_before
+        head = torch.tensor([[p_before], [n_before]], dtype=torch.int64, device=dev)
+        tpb_i, fpb_i = torch.cat([head[0], tp_i[:-1]]), torch.cat([head[1], fp_i[:-1]])
+        f64 = lambda t: t.to(torch.float64)
+        part = _aupr_terms(f64(tp_i - tpb_i), f64(tp_i), f64(fp_i), f64(tpb_i), f64(fpb_i)).reshape(1)
+    parts = _gather_fixed(part).flatten().tolist()
+    if P == 0 or N == 0:
+        return float("nan")
+    tot = 0.0
+    for v in parts:                                          # rank order: the same bits on every rank
+        tot += v
+    return tot / float(P)
 
 
 class Evaluator:
@@ -221,6 +342,23 @@ class AUCEvaluator(Evaluator):
         if self.distributed:
             return auc_distributed(s, self.flags, self.last_info)
         return auc_weighted(s, self.labels, None)  # MLlib AUC ignores weights
+
+
+class AUPREvaluator(Evaluator):
+    """Area under the precision/recall curve of all rows; unweighted like plain AUC (MLlib's ``areaUnderPR`` takes
+    no weights). Under a process group: :func:`aupr_distributed`."""
+    name = "AUPR"
+
+    def __init__(self, labels, offsets=None, weights=None, device=None):
+        super().__init__(labels, offsets, weights, device)
+        self.last_info: dict = {}
+        if self.distributed:
+            self.flags = (self.labels > POSITIVE_RESPONSE_THRESHOLD).to(torch.uint8)
+
+    def _evaluate(self, s):
+        if self.distributed:
+            return aupr_distributed(s, self.flags, self.last_info)
+        return aupr_weighted(s, self.labels, None)
 
 
 class RMSEEvaluator(Evaluator):
@@ -388,6 +526,19 @@ class AUCMultiEvaluator(MultiEvaluator):
         return self.ranking.auc(s)
 
 
+class AUPRMultiEvaluator(MultiEvaluator):
+    def __init__(self, id_tag: str, ids, labels, offsets=None, weights=None, device=None):
+        super().__init__(ids, labels, offsets, weights, device)
+        self.id_tag = id_tag
+        self.name = f"AUPR:{id_tag}"
+
+    def _local(self, s, y, w):
+        return aupr_weighted(s, y, w)
+
+    def _device_values(self, s):
+        return self.ranking.aupr(s)
+
+
 class PrecisionAtKMultiEvaluator(MultiEvaluator):
     def __init__(self, k: int, id_tag: str, ids, labels, offsets=None, weights=None, device=None):
         if k <= 0:
@@ -419,9 +570,10 @@ class EvaluatorType:
         return self.name
 
 
-SIMPLE_TYPES = ("AUC", "RMSE", "LOGISTIC_LOSS", "POISSON_LOSS", "SMOOTHED_HINGE_LOSS", "SQUARED_LOSS")
+SIMPLE_TYPES = ("AUC", "AUPR", "RMSE", "LOGISTIC_LOSS", "POISSON_LOSS", "SMOOTHED_HINGE_LOSS", "SQUARED_LOSS")
 _P_AT_K = re.compile(r"(?i:PRECISION)@(\d+):(.*)")
 _AUC_TAG = re.compile(r"(?i:AUC):(.*)")
+_AUPR_TAG = re.compile(r"(?i:AUPR):(.*)")
 
 
 def parse_evaluator_type(name: str) -> EvaluatorType:
@@ -436,6 +588,9 @@ def parse_evaluator_type(name: str) -> EvaluatorType:
     m = _AUC_TAG.fullmatch(n)
     if m:
         return EvaluatorType(f"AUC:{m.group(1)}", m.group(1))
+    m = _AUPR_TAG.fullmatch(n)
+    if m:
+        return EvaluatorType(f"AUPR:{m.group(1)}", m.group(1))
     up = n.upper()
     if up in SIMPLE_TYPES:
         return EvaluatorType(up)
@@ -446,9 +601,9 @@ def build_evaluator(etype, labels, offsets=None, weights=None, id_tags: Optional
     """EvaluatorFactory.buildEvaluator."""
     if isinstance(etype, str):
         etype = parse_evaluator_type(etype)
-    simple = {"AUC": AUCEvaluator, "RMSE": RMSEEvaluator, "LOGISTIC_LOSS": LogisticLossEvaluator,
-              "POISSON_LOSS": PoissonLossEvaluator, "SMOOTHED_HINGE_LOSS": SmoothedHingeLossEvaluator,
-              "SQUARED_LOSS": SquaredLossEvaluator}
+    simple = {"AUC": AUCEvaluator, "AUPR": AUPREvaluator, "RMSE": RMSEEvaluator,
+              "LOGISTIC_LOSS": LogisticLossEvaluator, "POISSON_LOSS": PoissonLossEvaluator,
+              "SMOOTHED_HINGE_LOSS": SmoothedHingeLossEvaluator, "SQUARED_LOSS": SquaredLossEvaluator}
     if not etype.is_multi:
         return simple[etype.name](labels, offsets, weights, device)
     if id_tags is None or etype.id_tag not in id_tags:
@@ -456,6 +611,8 @@ def build_evaluator(etype, labels, offsets=None, weights=None, id_tags: Optional
     ids = id_tags[etype.id_tag]
     if etype.k is not None:
         return PrecisionAtKMultiEvaluator(etype.k, etype.id_tag, ids, labels, offsets, weights, device)
+    if etype.name.startswith("AUPR:"):
+        return AUPRMultiEvaluator(etype.id_tag, ids, labels, offsets, weights, device)
     return AUCMultiEvaluator(etype.id_tag, ids, labels, offsets, weights, device)
 
 

@@ -1,4 +1,4 @@
-"""Device-resident per-group ranking metrics (K12: ``AUC:tag``, ``PRECISION@k:tag``).
+"""Device-resident per-group ranking metrics (K12: ``AUC:tag``, ``AUPR:tag``, ``PRECISION@k:tag``).
 
 :class:`GroupedRanking` is the group layout of one evaluator, built once: labels, weights and group ids never
 change between evaluations, so an evaluation only reads the scores (once, through ``perm``) and the group-ordered
@@ -20,7 +20,9 @@ A class takes no group longer than ``wg_max``, so a small ``wg_max`` pushes smal
 codes, labels and weights (a rank that owns nothing builds the empty layout, ``n = 0``).
 
 Reference: ``photon-api/.../evaluation/MultiEvaluator.scala:49-64``, ``AreaUnderROCCurveLocalEvaluator.scala:33-70``,
-``PrecisionAtKLocalEvaluator.scala:39-51``.
+``PrecisionAtKLocalEvaluator.scala:39-51``; the per-group area under the precision/recall curve is the weighted
+form of ``photon-diagnostics/.../Evaluation.scala:84`` (``evaluators.aupr_weighted``), a third metric of the same
+kernels over the same layout.
 """
 from __future__ import annotations
 
@@ -33,7 +35,7 @@ from ..ops.native import SEG_RANK_CLASSES, SEG_RANK_WG_CAP, seg_rank_caps, seg_r
 
 
 class GroupedRanking:
-    """Group layout for per-group AUC / precision@k. ``group_codes``: dense int64 group code of every row
+    """Group layout for per-group AUC / AUPR / precision@k. ``group_codes``: dense int64 group code of every row
     (``np.unique(..., return_inverse=True)``); ``labels`` / ``weights``: per row. On ``device="cpu"`` only the
     layout is built (the metrics are HIP kernels)."""
 
@@ -84,19 +86,24 @@ class GroupedRanking:
     def class_counts(self) -> Dict[str, int]:
         return {c: int(t.numel()) for c, t in self.lists.items()}
 
-    def _eval(self, scores, k: int):
+    def _eval(self, scores, k: int, metric=None):
         if self.device.type != "cuda":
             raise RuntimeError("GroupedRanking evaluates on a GPU only (HIP kernels); on the CPU it holds the "
                                "layout, use MultiEvaluator's host loop for values")
         s = torch.as_tensor(scores, dtype=torch.float64, device=self.device).contiguous()
         if s.numel() != self.n:
             raise ValueError(f"expected {self.n} scores, got {s.numel()}")
-        return seg_rank_eval(self, s, k)
+        return seg_rank_eval(self, s, k, metric)
 
     def auc(self, scores):
         """Weighted tie-grouped AUC of every group (fp64 device tensor, NaN where a class is missing); None when
         a score is NaN."""
         return self._eval(scores, 0)
+
+    def aupr(self, scores):
+        """Weighted tie-grouped area under the precision/recall curve of every group (``evaluators.aupr_weighted``;
+        fp64 device tensor, NaN where a class is missing); None when a score is NaN."""
+        return self._eval(scores, 0, "aupr")
 
     def precision_at_k(self, scores, k: int):
         """Precision@k of every group (fp64 device tensor); None when a score is NaN."""

@@ -11,8 +11,8 @@
 //     random projection (projector/ProjectionMatrix.scala:95-124);
 // * spmm_rows_kernel — K15 forward random projection X P^T of sparse rows (ProjectionMatrix.scala:48-63).
 // * downsample_kernel — K20 fixed-effect down-sampling as an on-device weight rewrite.
-// * seg_rank_wave_kernel / seg_rank_block_kernel — K12 per-group AUC and precision@k (AUC:tag, PRECISION@k:tag):
-//   every group sorted in registers / LDS and evaluated in one pass, one launch per size class.
+// * seg_rank_wave_kernel / seg_rank_block_kernel — K12 per-group AUC, AUPR and precision@k (AUC:tag, AUPR:tag,
+//   PRECISION@k:tag): every group sorted in registers / LDS and evaluated in one pass, one launch per size class.
 // * auc_count_kernel / auc_count_combine_kernel -- integer tie-group counts of the global AUC over one sorted score
 //   stream (plain AUC under a process group: every rank counts the score bucket it received).
 // * var_normal_kernel / var_scale_gram_kernel / chol_colnorm_kernel -- FULL coefficient variances diag(H_e^-1) of the
@@ -1338,8 +1338,12 @@ __global__ __launch_bounds__(FOLD_THREADS) void prior_fold_kernel(const long lon
 // positive / negative weight gp / gn that closes at sorted row i adds (P_i - gp) gn + gp gn / 2, P_i the inclusive
 // positive prefix; gp, gn are segmented scans (sums of non-negative terms, no differences of prefixes of gn), the
 // value is raw / (tp * tn) in exactly that expression (NaN when a class is missing). Precision@k counts positives
-// among the first min(k, L) sorted rows, over k. No atomics: scans and reductions are fixed shuffle / LDS trees, so
-// every launch gives the same bits. A NaN score sets *nan_flag (all writers store 1) and the wrapper discards the
+// among the first min(k, L) sorted rows, over k. AUPR (METRIC SR_AUPR) is the tie-grouped weighted trapezoid under
+// the precision/recall points (diagnostics/evaluation.py::binary_metrics with weights): the group that closes at
+// row i adds gp (p + q) / 2, p = P_i / (P_i + N_i) from the inclusive prefixes, q the same ratio of the prefixes
+// BEFORE the group's head (p when those are both 0), nothing when gp = 0; the value is sum / tp, NaN when a class
+// is missing. It shares the sort, the loads, the padding rows, the NaN flag and every index with AUC. No atomics:
+// scans and reductions are fixed shuffle / LDS trees, so every launch gives the same bits. A NaN score sets *nan_flag (all writers store 1) and the wrapper discards the
 // result; the compare-exchange evaluates ONE predicate per pair on both sides, so even then the indices stay a
 // permutation and nothing is read out of bounds.
 // Under a process group every rank runs these kernels over the rows it OWNS: MultiEvaluator routes each row once to
@@ -1357,17 +1361,43 @@ struct SegRankArgs {
   double* out;                  // [n_groups]
   int* nan_flag;
   long long n_list, n_rows, n_groups;
-  int k;                        // precision@k position (AUC: ignored)
+  int k;                        // precision@k position (AUC, AUPR: ignored)
 };
 
 #define SR_THREADS 256
 #define SR_WG_MAX 4096
+#define SR_PREC 0                 // METRIC of the kernels below: precision@k,
+#define SR_AUC 1                  // tie-grouped weighted ROC AUC,
+#define SR_AUPR 2                 // tie-grouped weighted area under the precision/recall curve
 
 __device__ __forceinline__ bool sr_before(double sa, int ia, double sb, int ib) {
   return sa > sb || (sa == sb && ia < ib);
 }
 
-template <int W, bool AUC>
+// The head-of-tie-group prefixes of AUPR: eP / eN are a lane's exclusive prefixes (the inclusive ones shifted up a
+// lane, 0 in the first lane of the row), heads the ballot of the lanes that open a tie group. Every lane gets the
+// pair of the last head at or before it; a lane with no head below it in the wave gets (0, 0) and the caller's
+// carry applies.
+__device__ __forceinline__ void sr_head_prefix(bool f0, int wl, double eP, double eN, double& hP, double& hN) {
+  const unsigned long long m = __ballot(f0) & (~0ull >> (63 - wl));
+  const int h = m ? 63 - __clzll((long long)m) : wl;
+  hP = __shfl(eP, h, 64);
+  hN = __shfl(eN, h, 64);
+  if (!m) { hP = 0.0; hN = 0.0; }
+}
+
+// One tie group's AUPR term, formed by its closing lane: gp (p + q) / 2 with p the precision after the group
+// (P, N: inclusive prefixes) and q the precision before it (hP, hN: prefixes before its head; p when nothing with
+// weight precedes it). A group without positive weight makes no recall step and adds nothing.
+__device__ __forceinline__ double sr_aupr_term(double gp, double P, double N, double hP, double hN) {
+  if (!(gp > 0.0)) return 0.0;
+  const double pr = P / (P + N);
+  const double den = hP + hN;
+  const double q = den > 0.0 ? hP / den : pr;
+  return gp * (pr + q) / 2.0;
+}
+
+template <int W, int METRIC>
 __global__ __launch_bounds__(SR_THREADS) void seg_rank_wave_kernel(SegRankArgs a) {
   const int l = threadIdx.x % W;
   const long long b = (long long)blockIdx.x * (SR_THREADS / W) + threadIdx.x / W;
@@ -1408,31 +1438,46 @@ __global__ __launch_bounds__(SR_THREADS) void seg_rank_wave_kernel(SegRankArgs a
   const double p0 = fl ? w : 0.0;
   const double n0 = w - p0;
   double val;
-  if (AUC) {
+  if (METRIC != SR_PREC) {
     const double p = __shfl(p0, idx, W), n = __shfl(n0, idx, W);
     const double sp = __shfl_up(s, 1, W), sn = __shfl_down(s, 1, W);
     // padding rows (-inf, weight 0) take part as ordinary rows: they add 0 to whatever tie group they join
     bool f = l == 0 || s != sp;
     const bool tail = l == W - 1 || s != sn;
-    double gp = p, gn = n, P = p;
+    const bool f0 = f;
+    double gp = p, gn = n, P = p, N = n;
 #pragma unroll
     for (int d = 1; d < W; d <<= 1) {
       const double tgp = __shfl_up(gp, d, W), tgn = __shfl_up(gn, d, W), tP = __shfl_up(P, d, W);
+      const double tN = METRIC == SR_AUPR ? __shfl_up(N, d, W) : 0.0;
       const int tf = __shfl_up((int)f, d, W);
       if (l >= d) {
         P += tP;
+        if (METRIC == SR_AUPR) N += tN;
         if (!f) { gp += tgp; gn += tgn; f = tf != 0; }
       }
     }
-    double raw = tail ? (P - gp) * gn + gp * gn / 2.0 : 0.0;
-    double tp = p, tn = n;
+    if (METRIC == SR_AUC) {
+      double raw = tail ? (P - gp) * gn + gp * gn / 2.0 : 0.0;
+      double tp = p, tn = n;
 #pragma unroll
-    for (int o = W / 2; o > 0; o >>= 1) {
-      raw += __shfl_xor(raw, o, W);
-      tp += __shfl_xor(tp, o, W);
-      tn += __shfl_xor(tn, o, W);
+      for (int o = W / 2; o > 0; o >>= 1) {
+        raw += __shfl_xor(raw, o, W);
+        tp += __shfl_xor(tp, o, W);
+        tn += __shfl_xor(tn, o, W);
+      }
+      val = raw / (tp * tn);
+    } else {
+      // lane 0 of every row opens a tie group, so the head found is one of this row's lanes
+      double eP = __shfl_up(P, 1, W), eN = __shfl_up(N, 1, W), hP, hN;
+      if (l == 0) { eP = 0.0; eN = 0.0; }
+      sr_head_prefix(f0, threadIdx.x & 63, eP, eN, hP, hN);
+      double sum = tail ? sr_aupr_term(gp, P, N, hP, hN) : 0.0;
+#pragma unroll
+      for (int o = W / 2; o > 0; o >>= 1) sum += __shfl_xor(sum, o, W);
+      const double tp = __shfl(P, W - 1, W), tn = __shfl(N, W - 1, W);
+      val = tp > 0.0 && tn > 0.0 ? sum / tp : (double)NAN;
     }
-    val = raw / (tp * tn);
   } else {
     const int fs = __shfl((int)fl, idx, W);
     int hit = (l < a.k && l < L) ? fs : 0;
@@ -1446,11 +1491,13 @@ __global__ __launch_bounds__(SR_THREADS) void seg_rank_wave_kernel(SegRankArgs a
 // CWG (PRE = false): sort the group in LDS, then evaluate the sorted rows in chunks of 256. LONG (PRE = true): the
 // rows are already sorted, the same chunk loop reads them from global memory. Carried across chunks (uniform in the
 // workgroup): total positive / negative weight, raw, and the open tie group's two sums -- a tie group may span
-// chunks; a row's neighbours are read directly, so no previous score is carried.
-template <bool PRE, bool AUC>
+// chunks; a row's neighbours are read directly, so no previous score is carried. AUPR also scans the negative
+// prefix and carries, with the open tie group, the two prefixes before its head (formed as running total + the
+// wave's exclusive prefix at the head, never as inclusive prefix - group sum); raw then holds the sum of its terms.
+template <bool PRE, int METRIC>
 __global__ __launch_bounds__(SR_THREADS) void seg_rank_block_kernel(SegRankArgs a, int npad_max) {
   extern __shared__ double sr_lds[];              // !PRE: keys [npad_max], then local indices [npad_max]
-  __shared__ double w_gp[4], w_gn[4], w_P[4], w_N[4], w_raw[4];
+  __shared__ double w_gp[4], w_gn[4], w_P[4], w_N[4], w_raw[4], w_hP[4], w_hN[4];
   __shared__ int w_f[4], w_hit[4];
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const long long b = blockIdx.x;
@@ -1501,7 +1548,7 @@ __global__ __launch_bounds__(SR_THREADS) void seg_rank_block_kernel(SegRankArgs 
       }
     }
   }
-  if (!AUC) {
+  if (METRIC == SR_PREC) {
     const long long kk = a.k < L ? a.k : L;
     int hit = 0;
     for (long long pos = tid; pos < (PRE ? L : kk); pos += SR_THREADS) {
@@ -1521,7 +1568,7 @@ __global__ __launch_bounds__(SR_THREADS) void seg_rank_block_kernel(SegRankArgs 
     if (tid == 0) a.out[g] = (double)(w_hit[0] + w_hit[1] + w_hit[2] + w_hit[3]) / (double)a.k;
     return;
   }
-  double TP = 0.0, TN = 0.0, RAW = 0.0, ogp = 0.0, ogn = 0.0;
+  double TP = 0.0, TN = 0.0, RAW = 0.0, ogp = 0.0, ogn = 0.0, ohP = 0.0, ohN = 0.0;
   for (long long c0 = 0; c0 < L; c0 += SR_THREADS) {
     const long long pos = c0 + tid;
     const bool valid = pos < L;
@@ -1552,41 +1599,76 @@ __global__ __launch_bounds__(SR_THREADS) void seg_rank_block_kernel(SegRankArgs 
       f = pos == 0 || s != sp;
       tail = pos == L - 1 || s != sn;
     }
+    const bool f0 = f;
     double gp = p, gn = n, P = p, N = n;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
       const double tgp = __shfl_up(gp, d, 64), tgn = __shfl_up(gn, d, 64), tP = __shfl_up(P, d, 64);
+      const double tN = METRIC == SR_AUPR ? __shfl_up(N, d, 64) : 0.0;
       const int tf = __shfl_up((int)f, d, 64);
       if (lane >= d) {
         P += tP;
+        if (METRIC == SR_AUPR) N += tN;
         if (!f) { gp += tgp; gn += tgn; f = tf != 0; }
       }
     }
+    double hP = 0.0, hN = 0.0;                    // AUPR: the wave-local prefixes before the lane's tie-group head
+    if (METRIC == SR_AUPR) {
+      double eP = __shfl_up(P, 1, 64), eN = __shfl_up(N, 1, 64);
+      if (lane == 0) { eP = 0.0; eN = 0.0; }
+      sr_head_prefix(f0, lane, eP, eN, hP, hN);
+    } else {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) N += __shfl_xor(N, o, 64);
-    if (lane == 63) { w_f[wv] = f; w_gp[wv] = gp; w_gn[wv] = gn; w_P[wv] = P; w_N[wv] = N; }
+      for (int o = 32; o > 0; o >>= 1) N += __shfl_xor(N, o, 64);
+    }
+    if (lane == 63) {                             // N: the wave's total either way (AUPR: its inclusive scan)
+      w_f[wv] = f; w_gp[wv] = gp; w_gn[wv] = gn; w_P[wv] = P; w_N[wv] = N;
+      if (METRIC == SR_AUPR) { w_hP[wv] = hP; w_hN[wv] = hN; }
+    }
     __syncthreads();
     double cp = ogp, cn = ogn, Pb = TP;           // what the waves (and chunks) before this one leave open
+    double Nb = TN, chP = ohP, chN = ohN;
     for (int v = 0; v < wv; ++v) {
-      if (w_f[v]) { cp = w_gp[v]; cn = w_gn[v]; } else { cp += w_gp[v]; cn += w_gn[v]; }
+      if (w_f[v]) {
+        cp = w_gp[v]; cn = w_gn[v];
+        if (METRIC == SR_AUPR) { chP = Pb + w_hP[v]; chN = Nb + w_hN[v]; }
+      } else {
+        cp += w_gp[v]; cn += w_gn[v];
+      }
       Pb += w_P[v];
+      if (METRIC == SR_AUPR) Nb += w_N[v];
     }
     if (!f) { gp += cp; gn += cn; }
     P += Pb;
-    double raw = tail ? (P - gp) * gn + gp * gn / 2.0 : 0.0;
+    double raw;
+    if (METRIC == SR_AUPR) {
+      if (f) { hP += Pb; hN += Nb; } else { hP = chP; hN = chN; }
+      N += Nb;
+      raw = tail ? sr_aupr_term(gp, P, N, hP, hN) : 0.0;
+    } else {
+      raw = tail ? (P - gp) * gn + gp * gn / 2.0 : 0.0;
+    }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) raw += __shfl_xor(raw, o, 64);
     if (lane == 0) w_raw[wv] = raw;
     __syncthreads();
     for (int v = 0; v < 4; ++v) {
-      if (w_f[v]) { ogp = w_gp[v]; ogn = w_gn[v]; } else { ogp += w_gp[v]; ogn += w_gn[v]; }
+      if (w_f[v]) {
+        ogp = w_gp[v]; ogn = w_gn[v];
+        if (METRIC == SR_AUPR) { ohP = TP + w_hP[v]; ohN = TN + w_hN[v]; }
+      } else {
+        ogp += w_gp[v]; ogn += w_gn[v];
+      }
       TP += w_P[v];
       TN += w_N[v];
       RAW += w_raw[v];
     }
     __syncthreads();
   }
-  if (tid == 0) a.out[g] = RAW / (TP * TN);
+  if (tid == 0) {
+    if (METRIC == SR_AUPR) a.out[g] = TP > 0.0 && TN > 0.0 ? RAW / TP : (double)NAN;
+    else a.out[g] = RAW / (TP * TN);
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1881,10 +1963,11 @@ int pml_auc_counts(const AucCountArgs* a, void* stream) {
 }
 
 // Per-group ranking metric of the groups a->list of one size class (cls 0: C16, 1: C64, 2: CWG, 3: LONG / pre-sorted)
-// into a->out; k = 0: AUC, k > 0: precision@k. npad_max (CWG): a power of two >= the longest listed group, <= 4096.
-int pml_seg_rank_eval(int cls, int k, const SegRankArgs* a, int npad_max, void* stream) {
+// into a->out; metric: SR_PREC (k > 0), SR_AUC or SR_AUPR (k ignored). npad_max (CWG): a power of two >= the
+// longest listed group, <= 4096.
+int pml_seg_rank_metric(int cls, int metric, int k, const SegRankArgs* a, int npad_max, void* stream) {
   if (a->n_list <= 0) return 0;
-  if (k < 0 || cls < 0 || cls > 3) return -22;
+  if (cls < 0 || cls > 3 || metric < SR_PREC || metric > SR_AUPR || (metric == SR_PREC ? k <= 0 : k < 0)) return -22;
   hipStream_t st = (hipStream_t)stream;
   SegRankArgs v = *a;
   v.k = k;
@@ -1892,23 +1975,32 @@ int pml_seg_rank_eval(int cls, int k, const SegRankArgs* a, int npad_max, void* 
   const long long blocks = (v.n_list + per - 1) / per;
   if (blocks > 0x7fffffffLL) return -22;
   const dim3 grid((unsigned)blocks), blk(SR_THREADS);
+#define SR_LAUNCH(KERNEL, A, LDS, ...)                                                                      \
+  do {                                                                                                      \
+    if (metric == SR_PREC) hipLaunchKernelGGL((KERNEL<A, SR_PREC>), grid, blk, LDS, st, __VA_ARGS__);       \
+    else if (metric == SR_AUC) hipLaunchKernelGGL((KERNEL<A, SR_AUC>), grid, blk, LDS, st, __VA_ARGS__);    \
+    else hipLaunchKernelGGL((KERNEL<A, SR_AUPR>), grid, blk, LDS, st, __VA_ARGS__);                         \
+  } while (0)
   if (cls == 0) {
-    if (k) hipLaunchKernelGGL((seg_rank_wave_kernel<16, false>), grid, blk, 0, st, v);
-    else hipLaunchKernelGGL((seg_rank_wave_kernel<16, true>), grid, blk, 0, st, v);
+    SR_LAUNCH(seg_rank_wave_kernel, 16, 0, v);
   } else if (cls == 1) {
-    if (k) hipLaunchKernelGGL((seg_rank_wave_kernel<64, false>), grid, blk, 0, st, v);
-    else hipLaunchKernelGGL((seg_rank_wave_kernel<64, true>), grid, blk, 0, st, v);
+    SR_LAUNCH(seg_rank_wave_kernel, 64, 0, v);
   } else if (cls == 2) {
     if (npad_max < 64 || npad_max > SR_WG_MAX || (npad_max & (npad_max - 1))) return -22;
     const size_t lds = (size_t)npad_max * (sizeof(double) + sizeof(int));
-    if (k) hipLaunchKernelGGL((seg_rank_block_kernel<false, false>), grid, blk, lds, st, v, npad_max);
-    else hipLaunchKernelGGL((seg_rank_block_kernel<false, true>), grid, blk, lds, st, v, npad_max);
+    SR_LAUNCH(seg_rank_block_kernel, false, lds, v, npad_max);
   } else {
-    if (k) hipLaunchKernelGGL((seg_rank_block_kernel<true, false>), grid, blk, 0, st, v, 0);
-    else hipLaunchKernelGGL((seg_rank_block_kernel<true, true>), grid, blk, 0, st, v, 0);
+    SR_LAUNCH(seg_rank_block_kernel, true, 0, v, 0);
   }
+#undef SR_LAUNCH
   LAUNCH_CHECK();
   return 0;
+}
+
+// The two metrics this entry point has always served: k = 0: AUC, k > 0: precision@k.
+int pml_seg_rank_eval(int cls, int k, const SegRankArgs* a, int npad_max, void* stream) {
+  if (k < 0) return -22;
+  return pml_seg_rank_metric(cls, k ? SR_PREC : SR_AUC, k, a, npad_max, stream);
 }
 
 int pml_downsample(int f64, const void* y, const void* w0, const long long* rowid, long long n,

@@ -823,6 +823,8 @@ def game_lib() -> Optional[ctypes.CDLL]:
         lib.pml_tl_compact.restype = c_int
         lib.pml_seg_rank_eval.argtypes = [c_int, c_int, ctypes.POINTER(SegRankArgs), c_int, c_void_p]
         lib.pml_seg_rank_eval.restype = c_int
+        lib.pml_seg_rank_metric.argtypes = [c_int, c_int, c_int, ctypes.POINTER(SegRankArgs), c_int, c_void_p]
+        lib.pml_seg_rank_metric.restype = c_int
         lib.pml_auc_counts.argtypes = [ctypes.POINTER(AucCountArgs), c_void_p]
         lib.pml_auc_counts.restype = c_int
         lib.pml_auc_count_block_rows.argtypes = []
@@ -967,6 +969,7 @@ def prior_fold(nip: torch.Tensor, pos: torch.Tensor, val: torch.Tensor, mu: torc
 
 SEG_RANK_CLASSES = ("C16", "C64", "CWG", "LONG")
 SEG_RANK_WG_CAP = 4096
+SEG_RANK_METRICS = {"precision": 0, "auc": 1, "aupr": 2}     # = SR_PREC / SR_AUC / SR_AUPR in game_kernels.hip
 
 
 def seg_rank_caps(wg_max: int) -> dict:
@@ -1015,16 +1018,23 @@ def check_seg_rank_layout(lay, scores: torch.Tensor) -> None:
         raise ValueError("seg_rank_eval: LONG row tables do not match seg_ptr")
 
 
-def seg_rank_eval(lay, scores: torch.Tensor, k: int = 0) -> Optional[torch.Tensor]:
+def seg_rank_eval(lay, scores: torch.Tensor, k: int = 0, metric: Optional[str] = None) -> Optional[torch.Tensor]:
     """Per-group ranking metric of ``scores`` (fp64, row order) over the group layout ``lay``
-    (:class:`~photon_ml_amd.evaluation.segmented.GroupedRanking`): weighted tie-grouped AUC (``k = 0``) or
-    precision@k, one fp64 value per group (NaN where undefined), from ``seg_rank_wave_kernel`` /
-    ``seg_rank_block_kernel`` -- one launch per populated size class. LONG groups (longer than ``lay.wg_max``) are
-    gathered and ordered here by two stable sorts (score descending, then group) and streamed by the pre-sorted
-    kernel. Returns None when a score is NaN (the caller falls back to the host loop). Deterministic."""
+    (:class:`~photon_ml_amd.evaluation.segmented.GroupedRanking`): weighted tie-grouped AUC (``k = 0``),
+    precision@k (``k > 0``) or, with ``metric="aupr"``, the weighted tie-grouped area under the precision/recall
+    curve (``evaluators.aupr_weighted``; ``k`` must stay 0). One fp64 value per group (NaN where undefined), from
+    ``seg_rank_wave_kernel`` / ``seg_rank_block_kernel`` -- one launch per populated size class. LONG groups (longer
+    than ``lay.wg_max``) are gathered and ordered here by two stable sorts (score descending, then group) and
+    streamed by the pre-sorted kernel. Returns None when a score is NaN (the caller falls back to the host loop).
+    Deterministic."""
     lib = require_game_lib()
     if k < 0:
         raise ValueError(f"seg_rank_eval: k must be >= 0: {k}")
+    if metric is None:
+        metric = "precision" if k else "auc"
+    if metric not in SEG_RANK_METRICS or (metric == "precision") != (k > 0):
+        raise ValueError(f"seg_rank_eval: metric {metric!r} with k = {k}")
+    mid = SEG_RANK_METRICS[metric]
     if not (scores.is_cuda and lay.perm.is_cuda):
         raise RuntimeError("seg_rank_eval needs the layout and the scores on a GPU")
     if os.environ.get("PML_CHECK_KERNEL_INPUTS", "0") == "1":
@@ -1041,7 +1051,8 @@ def seg_rank_eval(lay, scores: torch.Tensor, k: int = 0) -> Optional[torch.Tenso
         lst = lay.lists[name]
         if lst.numel():
             a.list, a.n_list = lst.data_ptr(), lst.numel()
-            check(lib.pml_seg_rank_eval(cls, int(k), ctypes.byref(a), int(lay.cwg_pad), st), f"seg_rank_eval {name}")
+            check(lib.pml_seg_rank_metric(cls, mid, int(k), ctypes.byref(a), int(lay.cwg_pad), st),
+                  f"seg_rank_eval {name}")
     lst = lay.lists["LONG"]
     if lst.numel():
         s = scores[lay.perm[lay.long_rows]] + 0.0            # -0.0 -> 0.0: the radix sort must see them tie
@@ -1054,7 +1065,7 @@ def seg_rank_eval(lay, scores: torch.Tensor, k: int = 0) -> Optional[torch.Tenso
                         list=lst.data_ptr(), lptr=lay.long_ptr.data_ptr(), out=out.data_ptr(),
                         nan_flag=nan_flag.data_ptr(), n_list=lst.numel(), n_rows=ss.numel(),
                         n_groups=lay.n_groups, k=int(k))
-        check(lib.pml_seg_rank_eval(3, int(k), ctypes.byref(b), 0, st), "seg_rank_eval LONG")
+        check(lib.pml_seg_rank_metric(3, mid, int(k), ctypes.byref(b), 0, st), "seg_rank_eval LONG")
     if int(nan_flag.item()):
         return None
     return out[:lay.n_groups]
