@@ -284,8 +284,15 @@ class RandomEffectCoordinate(Coordinate):
     def __init__(self, coordinate_id: str, data: GameData, data_config: RandomEffectDataConfiguration,
                  opt_config: GLMOptimizationConfiguration, task, compute_variance: bool = False, device=None,
                  dtype=torch.float64, entity_subset=None, layout: str = "auto",
-                 prior: Optional[RandomEffectModel] = None):
-        """``prior``: yesterday's model of this coordinate as a Gaussian prior (incremental training): the penalty
+                 prior: Optional[RandomEffectModel] = None, normalization: Optional[NormalizationContext] = None):
+        """``normalization``: the ``NormalizationContext`` of the coordinate's feature shard (None or an identity
+        context: none). The dataset folds it into the data once (``NormFold``): inside this coordinate every solver
+        state is the transformed-space ``w'`` (each entity's problem is solved over ``X' = (X - s) f``, the penalty is
+        on ``w'``), outside it everything stays in the original space. Scale-only contexts run every solver route on
+        the scaled data; a context with shifts runs the shifted fused TRON (``re_tron_csr_kernel<LOSS, true>``) or
+        the pass path.
+
+        ``prior``: yesterday's model of this coordinate as a Gaussian prior (incremental training): the penalty
         becomes ``lambda/2 sum_j (w_j - mu_j)^2 / sigma_j^2`` per entity and feature (``mu = 0, sigma^2 = 1`` where
         the prior model has no coefficient). The dataset folds it into the data once (``PriorFold``): inside this
         coordinate every solver state is ``v = (w - mu) / sigma`` under plain L2, outside it (models, scores,
@@ -298,6 +305,10 @@ class RandomEffectCoordinate(Coordinate):
         self.device = torch.device(device) if device is not None else default_device()
         self.has_prior = prior is not None
         self._entity_subset, self._prior = entity_subset, prior      # the dataset's build arguments (_restore_csr)
+        self.variance_type = VarianceComputationType.parse(compute_variance)
+        self._norm_ctx = None if normalization is None or normalization.is_identity else normalization
+        if self._norm_ctx is not None:
+            self._check_normalization_config(data_config)            # before the dataset is built
         if self.has_prior:
             if data_config.projector_type.kind.value == "RANDOM":
                 raise ValueError(f"coordinate {coordinate_id}: a prior model cannot be combined with the RANDOM "
@@ -305,8 +316,8 @@ class RandomEffectCoordinate(Coordinate):
             self._check_prior_config(opt_config)                     # before the dataset is built
         with phase(f"RE {coordinate_id} build: dataset"):
             self.dataset = RandomEffectDataset(data, data_config, self.device, dtype, entity_subset=entity_subset,
-                                               layout=layout, prior=prior)
-        self.variance_type = VarianceComputationType.parse(compute_variance)
+                                               layout=layout, prior=prior, normalization=self._norm_ctx)
+        self._check_intercepts()
         self.compute_variance = self.variance_type != VarianceComputationType.NONE
         self.base_offsets = torch.from_numpy(data.offsets).to(self.device)
         if self.has_prior:
@@ -351,6 +362,43 @@ class RandomEffectCoordinate(Coordinate):
 
     def _defer_stats(self, iters: torch.Tensor, reasons: torch.Tensor, act: torch.Tensor, seconds: float):
         self.__dict__["_stats_thunk"] = lambda: random_effect_tracker_stats(iters[act], reasons[act], seconds)
+
+    @property
+    def _norm(self):
+        """The dataset's ``NormFold`` (None without normalization)."""
+        return getattr(self.dataset, "norm", None)
+
+    @property
+    def _shifted(self) -> bool:
+        nf = self._norm
+        return nf is not None and nf.has_shift
+
+    def _check_normalization_config(self, data_config):
+        """What normalization of a random effect cannot be combined with (ValueError naming the coordinate, before
+        any training)."""
+        cid = self.coordinate_id
+        if self.has_prior:
+            raise ValueError(f"coordinate {cid}: normalization of a random effect cannot be combined with a prior "
+                             f"model on the same coordinate (the two transforms are not composed)")
+        if data_config.projector_type.kind.value == "RANDOM":
+            raise ValueError(f"coordinate {cid}: normalization of a random effect cannot be combined with the RANDOM "
+                             f"projector (the context lives on original-space features)")
+        if self._norm_ctx.shifts is not None and self.variance_type != VarianceComputationType.NONE:
+            raise ValueError(f"coordinate {cid}: coefficient variances ({self.variance_type.value}) are not supported "
+                             f"under a normalization with shifts (STANDARDIZATION); use a scale-only type")
+
+    def _check_intercepts(self):
+        """Under shifts every trained entity needs the intercept among its active features."""
+        nf = self._norm
+        if nf is None or not nf.has_shift:
+            return
+        ds = self.dataset
+        trained = torch.from_numpy(ds.n_active > 0)
+        missing = int((trained & (nf.i0.cpu() < 0)).sum())
+        if missing:
+            raise ValueError(f"coordinate {self.coordinate_id}: a normalization with shifts (STANDARDIZATION) needs an "
+                             f"intercept in every entity's model, {missing} of {int(trained.sum())} trained entities "
+                             f"have none among their active features")
 
     def _check_prior_config(self, opt_config: GLMOptimizationConfiguration):
         """What a prior cannot be combined with (ValueError naming the coordinate, before any training)."""
@@ -418,6 +466,28 @@ class RandomEffectCoordinate(Coordinate):
             W = torch.from_numpy(Wn).to(dev, dt)
             if bucket.mu is not None:                  # original space -> the solver's v = (w - mu) / sigma
                 W = (W - bucket.mu) / bucket.sigma
+            if bucket.nf is not None:                  # original space -> the transformed-space w'
+                W = self._bucket_to_transformed(bucket, W)
+        return W
+
+    @staticmethod
+    def _bucket_to_transformed(bucket, W: torch.Tensor) -> torch.Tensor:
+        """``T^-1`` per bucket row: ``w'_j = w_j / f_j``, ``w'_i0 = w_i0 + sum_j s_j w_j`` (``c_i0 = 0``, ``f_i0 = 1``)."""
+        V = W / bucket.nf
+        if bucket.nc is not None:
+            has = bucket.ni0 >= 0
+            V = V.clone()
+            b = torch.nonzero(has).squeeze(1)
+            V[b, bucket.ni0[b]] += (bucket.nc * V).sum(1)[b]
+        return V
+
+    @staticmethod
+    def _bucket_to_original(bucket, V: torch.Tensor) -> torch.Tensor:
+        """``T`` per bucket row: ``w_j = f_j w'_j``, ``w_i0 = w'_i0 - c . w'``."""
+        W = bucket.nf * V
+        if bucket.nc is not None:
+            b = torch.nonzero(bucket.ni0 >= 0).squeeze(1)
+            W[b, bucket.ni0[b]] -= (bucket.nc * V).sum(1)[b]
         return W
 
     def update_model(self, model: Optional[RandomEffectModel], partial_score: Optional[torch.Tensor] = None):
@@ -441,7 +511,7 @@ class RandomEffectCoordinate(Coordinate):
         iters, reasons = [], []
         self.last_variance_routes = {}
         t_start = time.time()
-        v_sq = 0.0
+        v_sq = v_abs = 0.0
         for b, bucket in enumerate(ds.buckets):
             O = ds.bucket_offsets(bucket, offs)
             bd = BatchedGLMData(bucket.X, bucket.y, O, bucket.w)
@@ -467,6 +537,11 @@ class RandomEffectCoordinate(Coordinate):
                 v_sq = v_sq + float(W.to(torch.float64).square().sum())
                 W = bucket.mu + bucket.sigma * W                       # w = mu + sigma v, var_w = sigma^2 var_v
                 var = None if var is None else bucket.sigma.square() * var
+            if bucket.nf is not None:
+                v_sq = v_sq + float(W.to(torch.float64).square().sum())
+                v_abs = v_abs + float(W.to(torch.float64).abs().sum())
+                W = self._bucket_to_original(bucket, W)                # w = T w' (scale only: var_w = f^2 var_w')
+                var = None if var is None else bucket.nf.square() * var
             k, v, vv = self._to_original(bucket, W, var)
             keys.append(k)
             vals.append(v)
@@ -480,7 +555,7 @@ class RandomEffectCoordinate(Coordinate):
         variances = np.concatenate(vars_) if vars_ else None
         out = RandomEffectModel(self.data_config.random_effect_type, self.data_config.feature_shard_id, self.task,
                                 ds.entity_ids, ds.dim, keys, vals, variances)
-        self._v_sq = (out, v_sq)
+        self._v_sq = (out, v_sq, v_abs)
         return out
 
     @property
@@ -658,7 +733,7 @@ class RandomEffectCoordinate(Coordinate):
         # the model keeps the projected keys (entity * dim + feature, sorted, aligned with W) without compaction:
         # W is dense in the projected space, and zeros are harmless (dropped at save, <1e-4 as in the reference);
         # compacting 1.25e9 coefficients per update was ~40 GB of traffic at config 5
-        v_sq = float(W.square().sum()) if self.has_prior else None
+        v_sq = float(W.square().sum()) if (self.has_prior or self._norm is not None) else None
         W, var = self._to_original_segmented(W, var)
         out = RandomEffectModel(self.data_config.random_effect_type, self.data_config.feature_shard_id, self.task,
                                 ds.entity_ids, ds.dim, ds.projection_keys_t, W, var)
@@ -681,7 +756,7 @@ class RandomEffectCoordinate(Coordinate):
         seg = ds.seg
         if fused_eligible(self.loss, opt, l1, oc.constraint_map, seg.y.device):
             kind = "tron"
-        elif fused_lbfgs_eligible(self.loss, opt, l1, oc.constraint_map, seg.y.device):
+        elif fused_lbfgs_eligible(self.loss, opt, l1, oc.constraint_map, seg.y.device, shift=self._shifted):
             kind = "lbfgs"
         else:
             return None
@@ -735,7 +810,8 @@ class RandomEffectCoordinate(Coordinate):
         ds = self.dataset
         with Timed(f"RE {self.coordinate_id}: segmented CSR rebuilt", log, logging.DEBUG):
             again = RandomEffectDataset(self.data, self.data_config, self.device, ds.dtype,
-                                        entity_subset=self._entity_subset, layout=ds.layout, prior=self._prior)
+                                        entity_subset=self._entity_subset, layout=ds.layout, prior=self._prior,
+                                        normalization=self._norm_ctx)
         csr = getattr(again, "_seg_csr", None)
         if csr is not None and int(csr[0].numel()) == int(ds.seg.y.numel()) + 1:
             ds._seg_csr = csr
@@ -749,6 +825,11 @@ class RandomEffectCoordinate(Coordinate):
         rs, fused, sub = comps
         out = {"row_space": 0 if rs is None else int(rs.B), "fused": 0 if fused is None else int(fused.B),
                "pass_path": 0 if sub is None else int(sub.entities.numel())}
+        if self._shifted:
+            # every fused entity on re_tron_csr_kernel<LOSS, true>; no row-space, lean, tall, Hessian or resident launch
+            out["shifted"] = True
+            out["fused_kernel"] = "re_tron_csr_kernel<LOSS, true>"
+            out["lean"] = out["hessian"] = 0
         if fused is not None:
             out["fused_launches"] = len(fused.launches)
             out["heavy_to_pass_path"] = int(fused.n_heavy)
@@ -912,9 +993,10 @@ class RandomEffectCoordinate(Coordinate):
             self._lazy_W = primal
             out = RandomEffectModel(self.data_config.random_effect_type, self.data_config.feature_shard_id,
                                     self.task, ds.entity_ids, ds.dim, ds.projection_keys_t,
-                                    self._original_thunk(primal), None, sum_sq=float(sum_sq))
+                                    self._original_thunk(primal), None,
+                                    sum_sq=None if self._norm is not None else float(sum_sq))
         self._last = (out, None)
-        self._v_sq = (out, float(sum_sq)) if self.has_prior else None
+        self._v_sq = (out, float(sum_sq)) if (self.has_prior or self._norm is not None) else None
         return out
 
     def _sub_inputs(self, sub, seg, W0) -> torch.Tensor:
@@ -940,7 +1022,7 @@ class RandomEffectCoordinate(Coordinate):
             res = batched_tron(sub.seg, self.loss, l2, W0s, oc.tolerance, oc.maximum_iterations)
         else:
             res = batched_lbfgs(sub.seg, self.loss, l2, W0s, oc.tolerance, oc.maximum_iterations, l1=l1)
-        return res, sub.seg.glm.matvec(res.W)
+        return res, sub.seg.xw(res.W)
 
     def _active_mask(self, device) -> torch.Tensor:
         """Entities with active data (bool, on ``device``; uploaded once)."""
@@ -976,7 +1058,8 @@ class RandomEffectCoordinate(Coordinate):
     def _row_space(self, l1: float, oc):
         """Row-space batch for the wide entities (built once per dataset), or None when not applicable."""
         from ..optimization.row_space import RowSpaceBatch, row_space_eligible
-        if os.environ.get("PML_RE_ROW_SPACE", "1") == "0" or not row_space_eligible(l1, oc.constraint_map):
+        if (os.environ.get("PML_RE_ROW_SPACE", "1") == "0"
+                or not row_space_eligible(l1, oc.constraint_map, shift=self._shifted)):
             return None
         if getattr(self, "_rs", None) is None:
             self._rs = RowSpaceBatch(self.dataset.seg, nmax=int(os.environ.get("PML_RS_NMAX", "128")),
@@ -1001,19 +1084,33 @@ class RandomEffectCoordinate(Coordinate):
         pr = ds.prior
         if pr is not None:                             # original space -> the solver's v = (w - mu) / sigma
             W = (W - pr.mu) / pr.sigma
+        nf = ds.norm
+        if nf is not None:                             # original space -> the transformed-space w' = T^-1 w
+            W = W / nf.f
+            if nf.c is not None:
+                seg = ds.seg                           # w'_i0 = w_i0 + sum_j s_j w_j = w_i0 + c . w' (c_i0 = 0)
+                W[seg._sh_idx] += seg.bdot(seg._sh_c, W.contiguous())[seg._sh_ent]
         return W
 
     def _to_original_segmented(self, V: torch.Tensor, var: Optional[torch.Tensor] = None):
         """Packed solver-space coefficients (and variances) as original-space ones: ``w = mu + sigma v``, ``var_w =
         sigma^2 var_v`` (exact for SIMPLE and FULL: ``H_w^-1 = S H_v^-1 S``). The inputs themselves without a prior."""
         pr = self.dataset.prior
+        nf = self.dataset.norm
+        if nf is not None:
+            # w = T w': w_j = f_j w'_j, w_i0 = w'_i0 - c . w'; scale only: var_w = f^2 var_w'
+            W = nf.f * V
+            if nf.c is not None:
+                seg = self.dataset.seg
+                W[seg._sh_idx] -= seg.bdot(seg._sh_c, V.contiguous())[seg._sh_ent]
+            return W, (None if var is None else nf.f.square() * var)
         if pr is None:
             return V, var
         return pr.mu + pr.sigma * V, (None if var is None else pr.sigma.square() * var)
 
     def _original_thunk(self, primal):
         """The lazy model's coefficient thunk in the original space (``primal`` itself without a prior)."""
-        if self.dataset.prior is None:
+        if self.dataset.prior is None and self.dataset.norm is None:
             return primal
         return lambda: self._to_original_segmented(primal())[0]
 
@@ -1059,7 +1156,7 @@ class RandomEffectCoordinate(Coordinate):
             # the model just solved: its active-row scores are one forward pass over the block-diagonal data
             # (or, when every entity was solved in its row space, L beta)
             rz = getattr(self, "_rs_scores", None)
-            z = rz if rz is not None else ds.seg.glm.matvec(last[1])
+            z = rz if rz is not None else ds.seg.xw(last[1])
             if getattr(ds, "seg_rows_identity", False) and z.numel() == self.data.n_rows:
                 out = z.clone()
             else:
@@ -1080,9 +1177,33 @@ class RandomEffectCoordinate(Coordinate):
         if self.has_prior:
             # lambda/2 sum (w - mu)^2 / sigma^2 = lambda/2 ||v||^2 (no L1 with a prior)
             return 0.5 * reg.l2_weight(lam) * self._prior_sum_sq(model)
+        if self._norm is not None:
+            # lambda/2 ||w'||^2 + lambda_1 ||w'||_1 over the transformed-space coefficients the solvers minimise
+            a, q = self._norm_sums(model, need_abs=l1w != 0)
+            return (l1w * a if l1w != 0 else 0.0) + 0.5 * reg.l2_weight(lam) * q
         a, q = model.sum_abs_and_sq(need_abs=l1w != 0)
         return (l1w * a if l1w != 0 else 0.0) + 0.5 * reg.l2_weight(lam) * q
 
+
+    def _norm_sums(self, model: RandomEffectModel, need_abs: bool):
+        """``(sum |w'|, sum w'^2)`` of ``model`` in the transformed space: the sum of squares kept from the solve for
+        the model returned last, both mapped from the model's coefficients otherwise."""
+        kept = getattr(self, "_v_sq", None)
+        if kept is not None and kept[0] is model and (not need_abs or len(kept) > 2):
+            return (float(kept[2]) if len(kept) > 2 else float("nan")), float(kept[1])
+        ds = self.dataset
+        saved, self._W = self._W, {}
+        try:
+            if ds.layout == "segmented":
+                V = self._warm_start_segmented(model).to(torch.float64)
+                return float(V.abs().sum()), float(V.square().sum())
+            a = q = 0.0
+            for b, bucket in enumerate(ds.buckets):
+                V = self._warm_start(b, bucket, model).to(torch.float64)
+                a, q = a + float(V.abs().sum()), q + float(V.square().sum())
+            return a, q
+        finally:
+            self._W = saved
 
     def _prior_sum_sq(self, model: RandomEffectModel) -> float:
         """``sum (w - mu)^2 / sigma^2`` of ``model`` over this coordinate's coefficients: kept from the solve for the
@@ -1126,10 +1247,16 @@ class ShardedRandomEffectCoordinate(Coordinate):
 
     def __init__(self, coordinate_id: str, data: GameData, data_config: RandomEffectDataConfiguration,
                  opt_config: GLMOptimizationConfiguration, task, compute_variance: bool = False, device=None,
-                 dtype=torch.float64, prior: Optional[RandomEffectModel] = None):
-        """``prior``: passed to the inner coordinate (the loaded model is whole on every rank; the lookup is by
+                 dtype=torch.float64, prior: Optional[RandomEffectModel] = None,
+                 normalization: Optional[NormalizationContext] = None):
+        """``normalization``: not supported under a process group (ValueError).
+
+        ``prior``: passed to the inner coordinate (the loaded model is whole on every rank; the lookup is by
         entity id, so each rank folds the priors of the entities it owns)."""
         from ..parallel.sharding import EntityPartitioner, RowRouter, entity_keys
+        if normalization is not None and not normalization.is_identity:
+            raise ValueError(f"coordinate {coordinate_id}: normalization of a random effect is not supported under a "
+                             f"process group")
         self.coordinate_id = coordinate_id
         self.data_config = data_config
         self.device = torch.device(device) if device is not None else default_device()

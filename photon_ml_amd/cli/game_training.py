@@ -148,6 +148,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--coordinate-update-sequence", required=True)
     p.add_argument("--coordinate-descent-iterations", type=int, required=True)
     p.add_argument("--normalization", default="NONE")
+    p.add_argument("--normalize-random-effects", type=parse_bool, default=False,
+                   help="apply --normalization to the random-effect coordinates too (one context per feature shard "
+                        "from the statistics of all rows; each entity is solved in the normalized space); default: "
+                        "random-effect coordinates ignore normalization")
     p.add_argument("--data-summary-directory")
     p.add_argument("--tree-aggregate-depth", type=int, default=1,
                    help="reduction depth of the reference's treeAggregate: >= 2 selects RCCL's tree all-reduce "
@@ -318,7 +322,8 @@ class GameTrainingDriver(GameDriverBase):
                              DataValidationType.parse(a.data_validation))
         # Statistics of a shard a fixed-effect coordinate trains on come from the estimator, which takes them from
         # the device copy it builds (GameEstimator.set_normalization) and hands them over as soon as the coordinates
-        # exist; every other shard is summarised here, on the host. Random-effect coordinates ignore normalization.
+        # exist; every other shard is summarised here, on the host. Random-effect coordinates ignore normalization
+        # unless --normalize-random-effects is on (GameEstimator.set_random_effect_normalization).
         def write_summary(sid, st):
             if a.data_summary_directory and rank() == 0:
                 d = os.path.join(a.data_summary_directory, sid)
@@ -351,7 +356,8 @@ class GameTrainingDriver(GameDriverBase):
                .set_warm_start(a.use_warm_start)
                .set_tree_aggregate_depth(a.tree_aggregate_depth)
                .set_normalization(self.normalization, {sid: m.intercept_index for sid, m in maps.items()},
-                                  collect_statistics=bool(a.data_summary_directory)))
+                                  collect_statistics=bool(a.data_summary_directory))
+               .set_random_effect_normalization(a.normalize_random_effects))
         est.coordinates_built_callback = coordinates_built
         if a.model_input_directory:
             from ..io.model_io import load_game_model

@@ -119,6 +119,9 @@ class Bucket:
     d_local: np.ndarray       # projected dim per entity
     mu: Optional[torch.Tensor] = None      # [B, d] prior means (0 on padding), None without a prior
     sigma: Optional[torch.Tensor] = None   # [B, d] prior standard deviations (1 on padding)
+    nf: Optional[torch.Tensor] = None      # [B, d] normalization factors (1 on padding), None without normalization
+    nc: Optional[torch.Tensor] = None      # [B, d] factor x shift (0 on padding and the intercept), None without shifts
+    ni0: Optional[torch.Tensor] = None     # [B] column of the intercept (-1: the entity has none), None without shifts
 
 
 @dataclass
@@ -132,6 +135,37 @@ class PriorFold:
     mu: Optional[torch.Tensor]
     sigma: Optional[torch.Tensor]
     row_margins: torch.Tensor
+
+
+@dataclass
+class NormFold:
+    """A per-shard ``NormalizationContext`` folded into a random-effect dataset: the solvers work on ``X' = (X - s) f``
+    and the coordinate maps ``w' <-> w`` at its boundary. ``f`` / ``c = f s``: per packed projected coefficient
+    (segmented layout; the dense layout keeps them per bucket), ``c`` None without shifts; ``i0``: per entity, the
+    position of the intercept inside its coefficient segment (-1: the context has no shifts, or the entity has no
+    intercept among its features). The factors are folded into the stored values (``X_F``); the shift stays on the
+    coefficient side: ``X' = X_F (I - e_i0 c^T)`` because column ``i0`` of ``X_F`` is all ones."""
+    f: Optional[torch.Tensor]
+    c: Optional[torch.Tensor]
+    i0: torch.Tensor
+    has_shift: bool = False
+
+
+def norm_lookup(ctx, feature: torch.Tensor):
+    """``(f, c)`` of the context gathered to the original features ``feature`` (on its device); ``c`` None without
+    shifts. A context without factors gives ``f = 1``."""
+    dev = feature.device
+    n = feature.numel()
+    f = (torch.ones(n, dtype=torch.float64, device=dev) if ctx.factors is None
+         else ctx.factors.to(dev, torch.float64)[feature])
+    if not (bool(torch.isfinite(f).all()) and bool((f > 0).all())):
+        raise ValueError("normalization factors must be finite and positive")
+    if ctx.shifts is None:
+        return f, None
+    s = ctx.shifts.to(dev, torch.float64)[feature]
+    if not bool(torch.isfinite(s).all()):
+        raise ValueError("normalization shifts must be finite")
+    return f, f * s
 
 
 def prior_lookup(prior, entity_ids: np.ndarray, dim: int, col_entity: torch.Tensor, col_feature: torch.Tensor):
@@ -220,8 +254,11 @@ class RandomEffectDataset:
 
     def __init__(self, data: GameData, config: RandomEffectDataConfiguration, device="cpu",
                  dtype=torch.float64, bucket_elems: int = 1 << 24, entity_subset: Optional[np.ndarray] = None,
-                 layout: str = "auto", prior=None):
-        """``prior``: a :class:`RandomEffectModel` whose means / variances become a Gaussian prior folded into the
+                 layout: str = "auto", prior=None, normalization=None):
+        """``normalization``: a ``NormalizationContext`` of the feature shard folded into the data once, here
+        (:class:`NormFold`, kept as ``self.norm``; None or an identity context: the data as it is).
+
+        ``prior``: a :class:`RandomEffectModel` whose means / variances become a Gaussian prior folded into the
         data once, here (:class:`PriorFold`, kept as ``self.prior``; None: plain L2).
 
         ``layout``: ``dense`` = size buckets of padded ``[B, n, d]`` problems (batched GEMMs); ``segmented`` =
@@ -232,6 +269,11 @@ class RandomEffectDataset:
         self.dtype = dtype
         self.prior = None
         self._prior_model = prior
+        self.norm = None
+        self._norm_ctx = None if normalization is None or normalization.is_identity else normalization
+        if self._norm_ctx is not None and (prior is not None or config.projector_type.kind == ProjectorKind.RANDOM):
+            raise ValueError("normalization of a random effect cannot be combined with a prior model or the RANDOM "
+                             "projector")
         if prior is not None and config.projector_type.kind == ProjectorKind.RANDOM:
             raise ValueError("a prior model cannot be combined with the RANDOM projector (the prior lives on "
                              "original-space coefficients)")
@@ -486,6 +528,13 @@ class RandomEffectDataset:
             X = np.zeros((B, nmax, dmax))
             X[slot_b[rr], slot_r[rr], cc] = vv
             mu_b = sg_b = None
+            nf_b = nc_b = ni0_b = None
+            if self._norm_ctx is not None:
+                # X' = (X - s) f materialised on the real rows (padding rows stay zero, padding columns f = 1, s = 0)
+                nf_b, nc_b, ni0_b = self._bucket_norm(be, d_local, dmax)
+                X[slot_b, slot_r] *= nf_b[slot_b]
+                if nc_b is not None:
+                    X[slot_b, slot_r] -= nc_b[slot_b]
             if self._prior_model is not None:
                 mu_b, sg_b = self._bucket_prior(be, d_local, dmax)
                 row_margins[active_rows[loc_rows]] = np.einsum("bnd,bd->bn", X, mu_b)[slot_b, slot_r]
@@ -500,10 +549,44 @@ class RandomEffectDataset:
             out.append(Bucket(be, torch.from_numpy(rows).to(dev), torch.from_numpy(X).to(dev, dt),
                               torch.from_numpy(Y).to(dev, dt), torch.from_numpy(W).to(dev, dt), d_local[be],
                               None if mu_b is None else torch.from_numpy(mu_b).to(dev, dt),
-                              None if sg_b is None else torch.from_numpy(sg_b).to(dev, dt)))
+                              None if sg_b is None else torch.from_numpy(sg_b).to(dev, dt),
+                              None if nf_b is None else torch.from_numpy(nf_b).to(dev, dt),
+                              None if nc_b is None else torch.from_numpy(nc_b).to(dev, dt),
+                              None if ni0_b is None else torch.from_numpy(ni0_b).to(dev)))
         if self._prior_model is not None:
             self.prior = PriorFold(None, None, torch.from_numpy(row_margins).to(dev))
+        if self._norm_ctx is not None:
+            i0 = np.full(n_ent, -1, dtype=np.int64)
+            for bk in out:
+                if bk.ni0 is not None:
+                    i0[bk.entities] = bk.ni0.cpu().numpy()
+            self.norm = NormFold(None, None, torch.from_numpy(i0), self._norm_ctx.shifts is not None)
         return out
+
+    def _bucket_norm(self, be: np.ndarray, d_local: np.ndarray, dmax: int):
+        """``(f, c, i0)`` of a dense bucket: [B, dmax] factors (1 on padding columns), [B, dmax] factor x shift (0
+        on padding) and [B] intercept columns (-1 without one); ``c`` and ``i0`` None without shifts."""
+        ctx = self._norm_ctx
+        dl = d_local[be]
+        b_idx = np.repeat(np.arange(len(be)), dl)
+        c_idx = np.concatenate([np.arange(x) for x in dl]) if len(be) else np.zeros(0, np.int64)
+        if self.projector_type.kind == ProjectorKind.INDEX_MAP:
+            ptr, feat = self.projection.ptr, self.projection.feat
+            gf = np.concatenate([feat[ptr[e]:ptr[e + 1]] for e in be]) if len(be) else np.zeros(0, np.int64)
+        else:
+            gf = c_idx
+        gf = np.asarray(gf, dtype=np.int64)
+        f, c = norm_lookup(ctx, torch.from_numpy(gf))
+        f_b = np.ones((len(be), dmax))
+        f_b[b_idx, c_idx] = f.numpy()
+        if c is None:
+            return f_b, None, None
+        c_b = np.zeros((len(be), dmax))
+        c_b[b_idx, c_idx] = c.numpy()
+        i0 = np.full(len(be), -1, dtype=np.int64)
+        hit = gf == int(ctx.intercept_id)
+        i0[b_idx[hit]] = c_idx[hit]
+        return f_b, c_b, i0
 
     def _bucket_prior(self, be: np.ndarray, d_local: np.ndarray, dmax: int):
         """``(mu, sigma)`` [B, dmax] of a dense bucket's projected coefficients (0 / 1 on padding columns)."""
@@ -545,6 +628,16 @@ class RandomEffectDataset:
             x_seg = sp.csr_matrix((vt.numpy(), x_seg.indices, x_seg.indptr), shape=x_seg.shape)
             rm = torch.zeros(self.n_rows, dtype=torch.float64).index_copy_(0, torch.from_numpy(rows), m)
             self.prior = PriorFold(mu.to(self.device), sigma.to(self.device), rm.to(self.device))
+        if self._norm_ctx is not None:
+            # the factors through the same fold (mu = 0, sigma = f), in place; the shift stays coefficient-side
+            from ..ops.native import prior_fold
+            nf = self._norm_fold(torch.from_numpy(self.projection.keys), n_ent)
+            vt = torch.from_numpy(x_seg.data.astype(np.float64))
+            prior_fold(torch.from_numpy(x_seg.indptr.astype(np.int64)), torch.from_numpy(x_seg.indices.astype(np.int64)),
+                       vt, torch.zeros_like(nf.f), nf.f)
+            x_seg = sp.csr_matrix((vt.numpy(), x_seg.indices, x_seg.indptr), shape=x_seg.shape)
+            dv = self.device
+            self.norm = NormFold(nf.f.to(dv), None if nf.c is None else nf.c.to(dv), nf.i0.to(dv), nf.has_shift)
         yy = np.asarray(y, dtype=np.float64)[rows]
         ww = np.asarray(wts, dtype=np.float64)[rows]
         glm = make_glm_data(LabeledData(x_seg, yy, np.zeros(len(rows)), ww), self.device, "f64", col_windows=True)
@@ -557,8 +650,28 @@ class RandomEffectDataset:
         self.seg = SegmentedGLMData(glm, torch.from_numpy(e_row.astype(np.int64)).to(dev),
                                     self.col_entity_t, n_ent,
                                     torch.from_numpy(yy).to(dev), torch.from_numpy(ww).to(dev),
-                                    torch.zeros(len(rows), dtype=torch.float64, device=dev))
+                                    torch.zeros(len(rows), dtype=torch.float64, device=dev), shift=self._seg_shift(dev))
         self.d_total = d_total
+
+    def _norm_fold(self, keys: torch.Tensor, n_ent: int) -> NormFold:
+        """The :class:`NormFold` of the sorted projection ``keys`` (``entity * D + feature``), on their device."""
+        ctx, D = self._norm_ctx, self.dim
+        f, c = norm_lookup(ctx, keys % D)
+        i0 = torch.full((n_ent,), -1, dtype=torch.int64, device=keys.device)
+        if c is not None and keys.numel():
+            ar = torch.arange(n_ent, dtype=torch.int64, device=keys.device)
+            ptr = torch.searchsorted(keys, ar * D)
+            want = ar * D + int(ctx.intercept_id)
+            pos = torch.searchsorted(keys, want).clamp(max=keys.numel() - 1)
+            i0 = torch.where(keys[pos] == want, pos - ptr, i0)
+        return NormFold(f, c, i0, c is not None)
+
+    def _seg_shift(self, dev):
+        """``(c, i0)`` for :class:`SegmentedGLMData` (None without shifts)."""
+        nf = self.norm
+        if nf is None or nf.c is None:
+            return None
+        return nf.c.to(dev), nf.i0.to(dev)
 
     def _make_segmented_device(self, x, xa, ea, ent, active_rows, passive_rows, y, wts, n_ent, prefetched=None):
         """Device build of the block-diagonal problem (K14 on the GPU): rows sorted by entity (stable), the
@@ -634,6 +747,13 @@ class RandomEffectDataset:
                 m = prior_fold(nip, pos.contiguous(), val, mu, sigma)
                 rm = torch.zeros(self.n_rows, dtype=torch.float64, device=dev).index_copy_(0, rows_t, m)
                 self.prior = PriorFold(mu, sigma, rm)
+        if self._norm_ctx is not None:
+            # the factors through the same fold at the same narrow point (mu = 0, sigma = f), in place
+            from ..ops.native import prior_fold
+            with phase("RE segmented: normalization fold"):
+                self.norm = self._norm_fold(ukeys, n_ent)
+                val = val.to(torch.float64).contiguous()
+                prior_fold(nip, pos.contiguous(), val, torch.zeros_like(self.norm.f), self.norm.f.contiguous())
         yy = torch.from_numpy(np.asarray(y, dtype=np.float64)).to(dev)[rows_t]
         ww = torch.from_numpy(np.asarray(wts, dtype=np.float64)).to(dev)[rows_t]
         sort_phase.__exit__(None, None, None)
@@ -654,7 +774,7 @@ class RandomEffectDataset:
         self.seg_rows_identity = bool(rows_t.numel() == len(y) and (
             rows_t.numel() == 0 or bool((rows_t == torch.arange(rows_t.numel(), device=dev)).all())))
         self.seg = SegmentedGLMData(glm, e_row, self.col_entity_t, n_ent, yy, ww,
-                                    torch.zeros_like(yy))
+                                    torch.zeros_like(yy), shift=self._seg_shift(dev))
         self.d_total = d_total
 
     def entity_subset(self, mask: torch.Tensor) -> "SegmentSubset":
@@ -680,8 +800,9 @@ class RandomEffectDataset:
             xs = sp.csr_matrix((sval.numpy(), spos.numpy(), sip.numpy()), shape=(row_sel.numel(), max(d_sub, 1)))
             glm = make_glm_data(_LD(xs, yy.numpy(), np.zeros(row_sel.numel()), ww.numpy()), dev, "f64",
                                 col_windows=True)
+        shift = None if seg.shift is None else (seg.shift[0][col_sel], seg.shift[1][mask])
         sub = SegmentedGLMData(glm, ent_new[seg.row_entity[row_sel]], ent_new[seg.col_entity[col_sel]], B, yy, ww,
-                               torch.zeros_like(yy))
+                               torch.zeros_like(yy), shift=shift)
         return SegmentSubset(sub, row_sel, col_sel, torch.nonzero(mask).squeeze(1))
 
     def entity_csr(self, mask: torch.Tensor):

@@ -63,6 +63,7 @@ class GameEstimator:
         self.normalization_type = NormalizationType.NONE          # see set_normalization
         self.intercept_indices_by_shard: Dict[str, Optional[int]] = {}
         self.collect_statistics = False
+        self.normalize_random_effects = False                     # see set_random_effect_normalization
         self.feature_statistics: Dict[str, BasicStatisticalSummary] = {}   # by feature shard id, filled by fit
         self.coordinates_built_callback = None
         self.variance_computation_type = VarianceComputationType.NONE   # compute_variance: its boolean view
@@ -111,11 +112,39 @@ class GameEstimator:
         intercept index (or None). ``collect_statistics``: compute and keep the statistics even when the type is
         NONE (a data summary without normalization). They stay readable in ``feature_statistics`` by shard id, and
         ``coordinates_built_callback(estimator)`` runs as soon as every coordinate is built, before the first
-        update. Random-effect coordinates ignore normalization."""
+        update. Random-effect coordinates ignore normalization unless
+        :meth:`set_random_effect_normalization` switches it on."""
         self.normalization_type = NormalizationType.parse(normalization_type)
         self.intercept_indices_by_shard = dict(intercept_indices_by_shard or {})
         self.collect_statistics = bool(collect_statistics)
         return self
+
+    def set_random_effect_normalization(self, b: bool):
+        """Normalization for random-effect coordinates too (default False: they ignore it). When on, every
+        random-effect coordinate gets a context: the explicit one of :meth:`set_coordinate_normalization_contexts`
+        if its id is there, otherwise one built by TYPE (:meth:`set_normalization`) from the statistics of its whole
+        feature shard over all rows -- per shard, not per entity -- computed on the host. Each entity's problem is
+        then solved in the normalized space (penalties on the transformed coefficients) and the model comes back in
+        the original space. Not combinable with a prior model on the same coordinate, the RANDOM projector or a
+        process group; a type with shifts (STANDARDIZATION) needs an intercept among every trained entity's features
+        and supports no coefficient variances (ValueError naming the coordinate, before any training)."""
+        self.normalize_random_effects = bool(b)
+        return self
+
+    def _random_effect_context(self, data: GameData, cid: str, shard_id: str) -> Optional[NormalizationContext]:
+        """The context of random-effect coordinate ``cid`` (None: it ignores normalization)."""
+        if not self.normalize_random_effects:
+            return None
+        explicit = self.coordinate_normalization_contexts.get(cid)
+        if explicit is not None:
+            return explicit
+        if self.normalization_type == NormalizationType.NONE:
+            return None
+        if is_dist():
+            raise ValueError(f"coordinate {cid}: normalization of a random effect is not supported under a process "
+                             f"group")
+        st = self._coordinate_statistics(data, shard_id, None)       # host path: the shard has no tiled copy
+        return NormalizationContext.build(self.normalization_type, st, self.intercept_indices_by_shard.get(shard_id))
 
     def _coordinate_statistics(self, data: GameData, shard_id: str, glm_data) -> BasicStatisticalSummary:
         if shard_id not in self.feature_statistics:
@@ -238,7 +267,8 @@ class GameEstimator:
             if isinstance(dc, RandomEffectDataConfiguration):
                 cls = ShardedRandomEffectCoordinate if is_dist() else RandomEffectCoordinate
                 coords[cid] = cls(cid, data, dc, oc, self.training_task, self.variance_computation_type, self.device,
-                                  prior=self._prior_for(cid, True))
+                                  prior=self._prior_for(cid, True),
+                                  normalization=self._random_effect_context(data, cid, dc.feature_shard_id))
             else:
                 explicit = self.coordinate_normalization_contexts.get(cid)
                 prior = self._prior_for(cid, False)

@@ -163,6 +163,8 @@ struct ReTronArgs {
   int max_iter, max_fail, max_cg, dmax;
   double* gsc;               // lean kernel: gradient at W, per coefficient (packed like W)
   const double* xf2;         // lean kernel, optional: ||X_e||_F^2 per entity (lazy zero-point gradient norm)
+  const double* nc;          // re_tron_csr_kernel<LOSS, true>: shift c = f s per coefficient (packed like W)
+  const int* ni0;            // re_tron_csr_kernel<LOSS, true>: entity-local intercept column per entity (c[i0] = 0)
 };
 
 // Loads through the global address space: a generic pointer read through the kernel-argument struct becomes a FLAT
@@ -468,7 +470,14 @@ __device__ __forceinline__ void row_pass_q(const ReTronArgs& a, long long r0, lo
   }
 }
 
-template <int LOSS>
+// SHIFT: the entity's design matrix is X' = X (I - e_i0 c^T) (the shift of a STANDARDIZATION context over the
+// factor-scaled rows; column i0 of X is the all-ones intercept, c[i0] = 0). Both hooks are coefficient-side: before a
+// row pass over vec the intercept slot holds vec[i0] - c.vec (one more workgroup sum, two more barriers per pass) and
+// is restored in the combine sweep; the sweep forms g_j - c_j g0 with g0 = the fixed-order sum of the wave
+// accumulators at i0. Thread i0 % RE_THREADS owns slot i0 everywhere outside the row pass, and it writes acc[i0] only
+// after the sweep's workgroup sum, so the other threads' g0 reads need no barrier of their own. c is read from
+// global memory (at dmax = 2048 the LDS is taken). The MODE 1 pass thus writes the true margins.
+template <int LOSS, bool SHIFT = false>
 __global__ __launch_bounds__(RE_THREADS) void re_tron_csr_kernel(ReTronArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int e = a.order[blockIdx.x];
@@ -489,32 +498,80 @@ __global__ __launch_bounds__(RE_THREADS) void re_tron_csr_kernel(ReTronArgs a) {
   double* Z[2] = {a.scr + 2 * a.n_rows, a.scr + 3 * a.n_rows};
   int cur = 0, parity = 0, npass = 0;
   double* Wg = a.W + c0;
+  // SHIFT only: the entity's c segment, its intercept slot (clamped into the segment) and that slot's owner thread
+  const double* cs = nullptr;
+  int i0 = 0;
+  bool own0 = false;
+  if constexpr (SHIFT) {
+    cs = a.nc + c0;
+    const int i = a.ni0[e];
+    i0 = i < 0 ? 0 : (i < d ? i : d - 1);
+    own0 = tid == i0 % RE_THREADS;
+  }
 
   auto zero_own = [&]() {
     for (int j = lane; j < d; j += 64) myacc[j] = 0.0;
   };
+  // SHIFT: vec[i0] -= c . vec ahead of a row pass over vec (every thread's writes of vec are behind a barrier);
+  // returns the saved vec[i0] in the owner thread. Ends with the barrier that publishes the slot to the row pass.
+  auto shift_in = [&](double* vec) -> double {
+    double s1[1] = {0.0};
+    for (int j = tid; j < d; j += RE_THREADS) s1[0] += gld(cs + j) * vec[j];
+    block_sums<1>(s1, red, parity);
+    double saved = 0.0;
+    if (own0) {
+      saved = vec[i0];
+      vec[i0] = saved - s1[0];
+    }
+    __syncthreads();
+    return saved;
+  };
+  // SHIFT: g0 = the combined accumulator at i0 (the same fixed wave order as the sweeps; broadcast LDS reads)
+  auto acc_i0 = [&]() -> double {
+    double g0 = acc[i0];
+#pragma unroll
+    for (int q = 1; q < RE_NW; ++q) g0 += acc[q * dm + i0];
+    return g0;
+  };
   // value + gradient at vec (MODE 1: writes D / Z buffer ``nb``); the gradient lands in acc[0 .. d). One sweep
   // combines the wave accumulators (fixed wave order) and forms ||vec||^2 and ||g||^2; three barriers in all.
-  auto value_grad = [&](const double* vec, int nb, bool at_zero, double& gg) -> double {
+  auto value_grad = [&](double* vec, int nb, bool at_zero, double& gg) -> double {
     ++npass;
     __syncthreads();
     zero_own();
+    double saved = 0.0;
+    if constexpr (SHIFT) {
+      if (!at_zero) saved = shift_in(vec);        // P 0 = 0 at the zero point
+    }
     double fp = 0.0;
     if (at_zero) row_pass<2, LOSS>(a, r0, r1, vec, myacc, nullptr, nullptr, nullptr, fp);
     else row_pass<1, LOSS>(a, r0, r1, vec, myacc, nullptr, D[nb], Z[nb], fp);
     __syncthreads();
     double s3[3] = {fp, 0.0, 0.0};
+    double g0 = 0.0, gi0 = 0.0;
+    if constexpr (SHIFT) g0 = acc_i0();
     for (int j = tid; j < d; j += RE_THREADS) {
       double g = acc[j];
 #pragma unroll
       for (int q = 1; q < RE_NW; ++q) g += acc[q * dm + j];
-      const double v = vec[j];
+      double v = vec[j];
+      if constexpr (SHIFT) {
+        g -= gld(cs + j) * g0;
+        if (j == i0 && !at_zero) {                // the unmodified vec for the L2 term and ||vec||^2
+          v = saved;
+          vec[j] = saved;
+        }
+      }
       g += a.l2 * v;
-      acc[j] = g;
+      if (SHIFT && j == i0) gi0 = g;              // written after the workgroup sum (others still read acc[i0])
+      else acc[j] = g;
       s3[1] += v * v;
       s3[2] += g * g;
     }
     block_sums<3>(s3, red, parity);
+    if constexpr (SHIFT) {
+      if (own0) acc[i0] = gi0;
+    }
     gg = s3[2];
     return s3[0] + 0.5 * a.l2 * s3[1];
   };
@@ -558,17 +615,29 @@ __global__ __launch_bounds__(RE_THREADS) void re_tron_csr_kernel(ReTronArgs a) {
       ++npass;
       __syncthreads();
       zero_own();
+      double saved = 0.0;
+      if constexpr (SHIFT) saved = shift_in(sD);
       double fp = 0.0;
       row_pass<0, LOSS>(a, r0, r1, sD, myacc, D[cur], nullptr, nullptr, fp);
       __syncthreads();
       double s5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+      double h0 = 0.0, hi0 = 0.0;
+      if constexpr (SHIFT) h0 = acc_i0();
       for (int j = tid; j < d; j += RE_THREADS) {
         double h = acc[j];
 #pragma unroll
         for (int q = 1; q < RE_NW; ++q) h += acc[q * dm + j];
-        const double dj = sD[j];
+        double dj = sD[j];
+        if constexpr (SHIFT) {
+          h -= gld(cs + j) * h0;
+          if (j == i0) {
+            dj = saved;
+            sD[j] = saved;
+          }
+        }
         h += a.l2 * dj;
-        acc[j] = h;
+        if (SHIFT && j == i0) hi0 = h;
+        else acc[j] = h;
         s5[0] += dj * h;
         s5[1] += sS[j] * dj;
         s5[2] += dj * dj;
@@ -576,6 +645,9 @@ __global__ __launch_bounds__(RE_THREADS) void re_tron_csr_kernel(ReTronArgs a) {
         s5[4] += h * h;
       }
       block_sums<5>(s5, red, parity);
+      if constexpr (SHIFT) {
+        if (own0) acc[i0] = hi0;
+      }
       const double dhd = s5[0], std_ = s5[1], dtd = s5[2], rh = s5[3], hh = s5[4];
       const double alpha = rtr / (dhd == 0.0 ? 1.0 : dhd);
       double tn = sts + 2.0 * alpha * std_ + alpha * alpha * dtd;
@@ -2222,6 +2294,31 @@ int pml_re_tron_csr(const int* order, int n_launch, const long long* row_ptr, co
   if (loss == LOSS_LOGISTIC) hipLaunchKernelGGL(re_tron_csr_kernel<0>, dim3(n_launch), dim3(RE_THREADS), smem, st, a);
   else if (loss == LOSS_POISSON) hipLaunchKernelGGL(re_tron_csr_kernel<1>, dim3(n_launch), dim3(RE_THREADS), smem, st, a);
   else hipLaunchKernelGGL(re_tron_csr_kernel<2>, dim3(n_launch), dim3(RE_THREADS), smem, st, a);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// pml_re_tron_csr with a normalization shift (re_tron_csr_kernel<LOSS, true>): ``nc`` = c per coefficient (packed
+// like W), ``ni0`` = entity-local intercept column per entity (0 <= i0 < d_e, c[i0] = 0).
+int pml_re_tron_csr_shift(const int* order, int n_launch, const long long* row_ptr, const long long* col_ptr,
+                          const long long* nip, const uint16_t* lcol, const double* val, const double* y,
+                          const double* off, const double* wt, double* scr, long long n_rows, double* W, double* f,
+                          int* iters, int* reason, double* zout, int* npass, int loss, double l2, double tol,
+                          int max_iter, int max_fail, int max_cg, int dmax, const double* nc, const int* ni0,
+                          hipStream_t st) {
+  if (n_launch <= 0) return 0;
+  if (dmax <= 0 || loss < 0 || loss > 2 || nc == nullptr || ni0 == nullptr) return -22;
+  const size_t smem = pml_re_tron_smem(dmax);
+  if (smem > 160 * 1024) return -22;
+  ReTronArgs a{order, n_launch, row_ptr, col_ptr, nip, lcol, val, y, off, wt, scr, n_rows, W, f, iters, reason,
+               zout, npass, loss, l2, tol, max_iter, max_fail, max_cg, dmax};
+  a.nc = nc;
+  a.ni0 = ni0;
+  if (loss == LOSS_LOGISTIC)
+    hipLaunchKernelGGL((re_tron_csr_kernel<0, true>), dim3(n_launch), dim3(RE_THREADS), smem, st, a);
+  else if (loss == LOSS_POISSON)
+    hipLaunchKernelGGL((re_tron_csr_kernel<1, true>), dim3(n_launch), dim3(RE_THREADS), smem, st, a);
+  else hipLaunchKernelGGL((re_tron_csr_kernel<2, true>), dim3(n_launch), dim3(RE_THREADS), smem, st, a);
   LAUNCH_CHECK();
   return 0;
 }

@@ -1612,6 +1612,8 @@ def re_lib() -> Optional[ctypes.CDLL]:
         lib.pml_re_tron_csr.argtypes = ([c_void_p, c_int] + [c_void_p] * 9 + [ctypes.c_longlong] + [c_void_p] * 6
                                         + [c_int, c_double, c_double, c_int, c_int, c_int, c_int, c_void_p])
         lib.pml_re_tron_csr.restype = c_int
+        lib.pml_re_tron_csr_shift.argtypes = lib.pml_re_tron_csr.argtypes[:-1] + [c_void_p, c_void_p, c_void_p]
+        lib.pml_re_tron_csr_shift.restype = c_int
         lib.pml_re_tron_smem.argtypes = [c_int]
         lib.pml_re_tron_smem.restype = ctypes.c_size_t
         lib.pml_re_tron_hess.argtypes = lib.pml_re_tron_csr.argtypes
@@ -1655,10 +1657,40 @@ def require_re_lib() -> ctypes.CDLL:
 RE_LEAN_DMAX = 1024 if os.environ.get("PML_RE_LEAN", "1") != "0" else 0
 
 
+def check_re_shift_inputs(order: torch.Tensor, col_ptr: torch.Tensor, c: torch.Tensor, i0: torch.Tensor) -> None:
+    """Host-side check of what ``re_tron_csr_kernel<LOSS, true>`` indexes by and relies on
+    (``PML_CHECK_KERNEL_INPUTS=1``): for every launched entity ``0 <= i0 < d_e``, ``c`` finite and ``c[i0] = 0`` (the
+    intercept is not shifted). Raises ValueError; nothing is launched."""
+    n_ent = int(col_ptr.numel()) - 1
+    if c.numel() != int(col_ptr[-1]) or i0.numel() != n_ent:
+        raise ValueError(f"re_tron shift: {c.numel()} shift values for {int(col_ptr[-1])} coefficients, {i0.numel()} "
+                         f"intercept columns for {n_ent} entities")
+    if not order.numel():
+        return
+    oe = order.to(torch.int64)
+    if int(oe.min()) < 0 or int(oe.max()) >= n_ent:
+        raise ValueError("re_tron shift: launch order out of range")
+    de = col_ptr[oe + 1] - col_ptr[oe]
+    ii = i0.to(torch.int64)[oe]
+    bad = (ii < 0) | (ii >= de)
+    if bool(bad.any()):
+        k = int(torch.nonzero(bad)[0])
+        raise ValueError(f"re_tron shift: intercept column {int(ii[k])} of entity {int(oe[k])} outside [0, "
+                         f"{int(de[k])})")
+    if not bool(torch.isfinite(c).all()):
+        raise ValueError("re_tron shift: shift values must be finite")
+    ci = c[col_ptr[oe] + ii]
+    if bool((ci != 0).any()):
+        k = int(torch.nonzero(ci != 0)[0])
+        raise ValueError(f"re_tron shift: the intercept of entity {int(oe[k])} carries a shift of {float(ci[k])} "
+                         f"(must be 0)")
+
+
 def re_tron_csr(order, row_ptr, col_ptr, nip, lcol, val, y, off, wt, scr, W, f, iters, reason, zout, loss_id: int,
                 l2: float, tol: float, max_iter: int, max_fail: int, max_cg: int, dmax: int,
                 npass: Optional[torch.Tensor] = None, hessian: bool = False, gsc: Optional[torch.Tensor] = None,
-                lean: Optional[bool] = None, quad: bool = False, xf2: Optional[torch.Tensor] = None) -> None:
+                lean: Optional[bool] = None, quad: bool = False, xf2: Optional[torch.Tensor] = None,
+                shift=None) -> None:
     """Fused per-entity primal TRON over the entities ``order`` (int32; one workgroup each) of a block-diagonal
     CSR (``re_tron_csr_kernel``). Entity ``e`` owns rows ``row_ptr[e]:row_ptr[e+1]`` (int64) and coefficients
     ``col_ptr[e]:col_ptr[e+1]`` of the packed ``W`` (fp64, in: warm start, out: solution); ``nip`` int64 row
@@ -1671,8 +1703,17 @@ def re_tron_csr(order, row_ptr, col_ptr, nip, lcol, val, y, off, wt, scr, W, f, 
     allocated when None); ``quad``: every row of the batch is padded to whole quads of 4 entries (column 0, value
     0.0), and the lean kernel reads 4 columns / 4 values per lane load (row_pass_q). ``xf2`` (lean only, optional,
     fp64 per entity): ``||X_e||_F^2``; a warm start then scales its gradient tolerance by the bound
-    ``||X_e||_F ||c||`` of ``||g(0)||`` and runs the pass at zero only if a gradient norm reaches it. Device only; in
-    place, nothing returned."""
+    ``||X_e||_F ||c||`` of ``||g(0)||`` and runs the pass at zero only if a gradient norm reaches it. ``shift`` =
+    ``(c, i0)`` (fp64 packed like ``W``; int32 per entity, the entity-local intercept column): the entity's design
+    matrix is ``X (I - e_i0 c^T)`` (``re_tron_csr_kernel<LOSS, true>``: the streaming kernel only, not ``hessian``
+    / ``lean``). Device only; in place, nothing returned."""
+    if shift is not None:
+        if hessian or lean:
+            raise ValueError("re_tron_csr: a shift runs on the streaming kernel only (not hessian / lean)")
+        lean = False
+        sc, si0 = shift
+        if os.environ.get("PML_CHECK_KERNEL_INPUTS", "0") == "1":
+            check_re_shift_inputs(order, col_ptr, sc, si0)
     lib = require_re_lib()
     n_rows = y.numel()
     B = int(order.numel())
@@ -1717,6 +1758,14 @@ def re_tron_csr(order, row_ptr, col_ptr, nip, lcol, val, y, off, wt, scr, W, f, 
             assert xf2.is_cuda and xf2.dtype == torch.float64 and xf2.numel() == n_ent and xf2.is_contiguous()
         check(lib.pml_re_tron_lean(*args, gsc.data_ptr(), int(bool(quad)), None if xf2 is None else xf2.data_ptr(),
                                    stream_handle(W.device)), "re_tron_lean")
+        return
+    if shift is not None:
+        for t in (sc, si0):
+            assert t.is_cuda and t.is_contiguous() and t.device == W.device
+        assert sc.dtype == torch.float64 and sc.numel() == W.numel()
+        assert si0.dtype == torch.int32 and si0.numel() == n_ent
+        check(lib.pml_re_tron_csr_shift(*args, sc.data_ptr(), si0.data_ptr(), stream_handle(W.device)),
+              "re_tron_csr_shift")
         return
     fn = lib.pml_re_tron_hess if hessian else lib.pml_re_tron_csr
     check(fn(*args, stream_handle(W.device)), "re_tron_csr")

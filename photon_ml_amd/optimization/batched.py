@@ -128,10 +128,16 @@ class SegmentedGLMData:
     segment sums. The matrix products run on the GLM HIP kernels (``matvec`` = forward pass, ``rmatvec`` =
     transpose pass over column tiles / windows) — no padding, any mix of entity sizes, one launch sequence for all
     entities (reference ``SingleNodeOptimizationProblem`` per entity).
+
+    ``shift`` = ``(c, i0)`` (``c`` per block column, ``i0`` per entity: the intercept's position inside the entity's
+    coefficient range, -1 for none): the design matrix is then ``X' = X (I - e_i0 c^T)`` per entity -- the shift of a
+    STANDARDIZATION context, whose factors the stored values already carry (``data.random_effect.NormFold``). It
+    is applied on the coefficient side: ``X' v = X (P v)`` with ``(P v)_i0 = v_i0 - c.v``, and ``X'^T r = P^T (X^T
+    r)`` with ``(P^T g)_j = g_j - c_j g_i0``, through the per-entity reductions below.
     """
 
     def __init__(self, glm, row_entity: torch.Tensor, col_entity: torch.Tensor, n_entities: int, y: torch.Tensor,
-                 weights: torch.Tensor, offsets: torch.Tensor):
+                 weights: torch.Tensor, offsets: torch.Tensor, shift=None):
         self.glm = glm
         self.row_entity = row_entity  # sorted: rows grouped by entity
         self.col_entity = col_entity  # sorted: each entity's coefficients are contiguous
@@ -143,10 +149,38 @@ class SegmentedGLMData:
         self.col_ptr = torch.searchsorted(col_entity, ar).to(torch.int64)
         self._dzz_key = None
         self._dzz = None
+        self.shift = None
+        if shift is not None:
+            c, i0 = shift[0].to(dev, torch.float64), shift[1].to(dev, torch.int64)
+            has = i0 >= 0
+            # entities without an intercept get c = 0 (P = I); the others' intercept as a packed column index
+            self._sh_c = torch.where(has[col_entity], c, torch.zeros_like(c)).contiguous()
+            self._sh_ent = torch.nonzero(has).squeeze(1)
+            self._sh_idx = self.col_ptr[self._sh_ent] + i0[self._sh_ent]
+            self.shift = (c, i0)
 
     @property
     def n_batch(self) -> int:
         return self.B
+
+    def _pv(self, v):
+        """``P v``: the intercept component of every entity less ``c . v`` (a new tensor)."""
+        out = v.clone()
+        out[self._sh_idx] -= self.bdot(self._sh_c, v.contiguous())[self._sh_ent]
+        return out
+
+    def _pt(self, g):
+        """``P^T g``: ``g_j - c_j g_i0`` per entity."""
+        g0 = torch.zeros(self.B, dtype=g.dtype, device=g.device).index_copy_(0, self._sh_ent, g[self._sh_idx])
+        return g - self._sh_c * self.bexp(g0)
+
+    def xw(self, W):
+        """``X' W`` of every row (no offsets)."""
+        return self.glm.matvec(W if self.shift is None else self._pv(W))
+
+    def _xt(self, r, **kw):
+        g = self.glm.rmatvec(r, **kw)
+        return g if self.shift is None else self._pt(g)
 
     # per-entity reductions over contiguous segments: deterministic segmented kernel (no scatter atomics)
     def bdot(self, a, b):
@@ -193,13 +227,13 @@ class SegmentedGLMData:
 
     def margins(self, W, active=None):
         self._set_active(active)
-        return self.glm.matvec(W) + self.o
+        return self.xw(W) + self.o
 
     def value_grad(self, loss, W, l2: float, active=None):
         z = self.margins(W, active)
         l, dl = loss.loss_and_dz(z, self.y)
         f = self._rowsum(weighted(self.w, l))
-        g = self.glm.rmatvec(weighted(self.w, dl))
+        g = self._xt(weighted(self.w, dl))
         if l2 > 0:
             f = f + 0.5 * l2 * self.bdot(W, W)
             g = g + l2 * W
@@ -215,19 +249,24 @@ class SegmentedGLMData:
         if (key is not None and key[0] is W and key[1] == W._version and key[2] is loss
                 and (key[3] is None or mk is not None)):
             return self._dzz
-        self._dzz = weighted(self.w, loss.dzz(self.glm.matvec(W) + self.o, self.y))
+        self._dzz = weighted(self.w, loss.dzz(self.xw(W) + self.o, self.y))
         self._dzz_key = (W, W._version, loss, None if mk is None else True)
         return self._dzz
 
     def hv(self, loss, W, V, l2: float, active=None):
         self._set_active(active)
         D = self._dzz_at(loss, W)
-        h = self.glm.rmatvec(D * self.glm.matvec(V))
+        h = self._xt(D * self.xw(V))
         return h + l2 * V if l2 > 0 else h
 
     def hdiag(self, loss, W, l2: float):
         D = weighted(self.w, loss.dzz(self.margins(W), self.y))
         h = self.glm.rmatvec(D, square=True)
+        if self.shift is not None:
+            # sum_i D_i (x_ij - c_j)^2 (column i0 of X is all ones): one more transpose pass for sum_i D_i x_ij
+            t = self.glm.rmatvec(D)
+            t0 = torch.zeros(self.B, dtype=t.dtype, device=t.device).index_copy_(0, self._sh_ent, t[self._sh_idx])
+            h = h - 2.0 * self._sh_c * t + self._sh_c.square() * self.bexp(t0)
         return h + l2 if l2 > 0 else h
 
 

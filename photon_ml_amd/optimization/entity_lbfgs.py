@@ -26,9 +26,10 @@ from .entity_tron import _CLASSES, FUSED_DMAX, FUSED_MAX_ROWS, FusedResult, fuse
 LBFGS_LOSSES = (0, 1, 2, 3)          # logistic, Poisson, squared, smoothed hinge (first-order solver)
 
 
-def fused_lbfgs_eligible(loss, optimizer: str, l1: float, constraints, device) -> bool:
-    """The fused OWL-QN applies to L-BFGS with an L1 weight (L1 / elastic net) on the GPU, without constraints."""
-    return (fused_enabled() and optimizer == "LBFGS" and l1 > 0 and not constraints
+def fused_lbfgs_eligible(loss, optimizer: str, l1: float, constraints, device, shift: bool = False) -> bool:
+    """The fused OWL-QN applies to L-BFGS with an L1 weight (L1 / elastic net) on the GPU, without constraints and
+    without a normalization shift in the data (``SegmentedGLMData.shift``: the pass path takes those)."""
+    return (fused_enabled() and optimizer == "LBFGS" and l1 > 0 and not constraints and not shift
             and torch.device(device).type == "cuda" and getattr(loss, "loss_id", -1) in LBFGS_LOSSES)
 
 

@@ -108,11 +108,17 @@ class EntityTronBatch:
 
     ``mask`` [E] bool: candidate entities (e.g. not handled in their row space). Entities with data and
     ``d_e <= FUSED_DMAX``, ``n_e <= FUSED_MAX_ROWS`` are taken (``self.mask``); ``ents`` / ``rows`` / ``cols``
-    are their parent entity indices, parent row positions and parent coefficient positions."""
+    are their parent entity indices, parent row positions and parent coefficient positions.
+
+    When the data carries a normalization shift (``seg.shift``) every class, dm <= 1024 included, launches
+    ``re_tron_csr_kernel<LOSS, true>`` with the batch's own ``c`` (gathered by ``cols``) and per-entity intercept
+    column; the lean, tall, Hessian and resident kernels are never launched."""
 
     def __init__(self, ds, mask: torch.Tensor):
         seg = ds.seg
         dev = seg.y.device
+        shifted = getattr(seg, "shift", None) is not None
+        self.shift = None
         n_e = seg.row_ptr[1:] - seg.row_ptr[:-1]
         d_e = seg.col_ptr[1:] - seg.col_ptr[:-1]
         # the kernels address an entity's entries with 32-bit offsets from its first entry
@@ -125,7 +131,7 @@ class EntityTronBatch:
         if e_nnz is not None:
             sel &= e_nnz.to(dev) < (1 << 31)
         self.n_heavy = 0
-        if RESIDENT == "auto" and dev.type == "cuda" and getattr(ds, "_seg_csr", None) is not None:
+        if RESIDENT == "auto" and dev.type == "cuda" and getattr(ds, "_seg_csr", None) is not None and not shifted:
             # tail entities too long for one register-resident launch (more rows than RES_KMAX workgroups hold,
             # or wider than its LDS image): one streaming workgroup would outlast the whole launch, so they go to
             # the block-diagonal pass path (grid-wide passes, run on its own stream next to this launch)
@@ -164,7 +170,7 @@ class EntityTronBatch:
             row_nnz = pnip[row_sel + 1] - pnip[row_sel]
             nnz = int(row_nnz.sum())
             self.quad = (nnz > 0 and nnz >= QUAD_MIN_ROW_NNZ * n_rows and os.environ.get("PML_RE_QUAD", "1") != "0"
-                         and not bool((de <= HESS_DMAX).any()))
+                         and not bool((de <= HESS_DMAX).any()) and not shifted)
             plen = (row_nnz + 3) // 4 * 4 if self.quad else row_nnz
             nip = torch.zeros(n_rows + 1, dtype=torch.int64, device=dev)
             torch.cumsum(plen, 0, out=nip[1:])
@@ -189,11 +195,18 @@ class EntityTronBatch:
             # (not with tall-narrow launches: re_tron_tall_kernel stages rows by ASSIGNMENT into a dense block,
             # where a column-0 padding entry could overwrite the real column 0)
             self.quad = (nnz > 0 and nnz >= QUAD_MIN_ROW_NNZ * n_rows and os.environ.get("PML_RE_QUAD", "1") != "0"
-                         and not bool((de <= HESS_DMAX).any()))
+                         and not bool((de <= HESS_DMAX).any()) and not shifted)
             if self.quad:
                 self.nip, self.lcol, self.val = pad_rows_to_quads(self.nip, self.lcol, self.val)
                 nip = self.nip
         self.rows, self.cols = row_sel, col_sel
+        if shifted:
+            # c in the batch's own packed column layout, the intercept's entity-local column per batch entity
+            c_all, i0_all = seg.shift
+            i0 = i0_all[self.ents]
+            if bool(((i0 < 0) | (i0 >= de)).any()):
+                raise ValueError("shifted fused TRON: an entity has no intercept column inside its coefficient range")
+            self.shift = (c_all[col_sel].to(torch.float64).contiguous(), i0.to(torch.int32).contiguous())
         row_ent = torch.repeat_interleave(torch.arange(self.B, device=dev), ne, output_size=n_rows)
         self.y, self.w = seg.y[row_sel].contiguous(), seg.w[row_sel].contiguous()
         self.n_rows = n_rows
@@ -212,11 +225,11 @@ class EntityTronBatch:
         if nnz and int(ent_nnz.max()) >= (1 << 31):
             raise ValueError("an entity of the fused batch has >= 2^31 non-zeros (32-bit kernel offsets)")
         self.launches = []
-        hess = de <= HESS_DMAX
+        hess = (de <= HESS_DMAX) & (not shifted)
         # register-resident tasks (one persistent launch): clusters (k > 1 workgroups) first, largest first
         self.res = None
         stream_sel = ~hess
-        if RESIDENT != "0" and bool(stream_sel.any()):
+        if RESIDENT != "0" and bool(stream_sel.any()) and not shifted:
             from ..ops.native import re_res_params
             cap, rdmax, grid = re_res_params()
             kmax = min(RES_KMAX, grid // 2)
@@ -249,8 +262,8 @@ class EntityTronBatch:
                 if idx.numel() == 0:
                     continue
                 order = idx[torch.argsort(ent_nnz[idx], descending=True, stable=True)]
-                self.launches.append((_launch_dmax(dm, de[idx], is_h), order.to(torch.int32).contiguous(),
-                                      bool(is_h)))
+                self.launches.append((dm if shifted else _launch_dmax(dm, de[idx], is_h),
+                                      order.to(torch.int32).contiguous(), bool(is_h)))
 
     def solve(self, loss, l2: float, W0: Optional[torch.Tensor], offsets: torch.Tensor, tol: float, max_iter: int,
               max_fail: int = 5, max_cg: int = 20) -> FusedResult:
@@ -276,6 +289,11 @@ class EntityTronBatch:
                               self.val, self.y, off, self.w, W, f, iters, reason, z, loss.loss_id, l2, tol, max_iter,
                               max_fail, max_cg)
         for dm, order, is_h in self.launches:
+            if self.shift is not None:
+                re_tron_csr(order, self.row_ptr, self.col_ptr, self.nip, self.lcol, self.val, self.y, off, self.w,
+                            self.scr, W, f, iters, reason, z, loss.loss_id, l2, tol, max_iter, max_fail, max_cg, dm,
+                            lean=False, shift=self.shift)
+                continue
             re_tron_csr(order, self.row_ptr, self.col_ptr, self.nip, self.lcol, self.val, self.y, off, self.w,
                         self.scr, W, f, iters, reason, z, loss.loss_id, l2, tol, max_iter, max_fail, max_cg, dm,
                         hessian=is_h, gsc=self.gsc, quad=self.quad, xf2=self.xf2)

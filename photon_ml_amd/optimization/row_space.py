@@ -71,8 +71,10 @@ def _canonical_csr(csr, dev):
     return nip.to(torch.int64), pos.to(torch.int64), val.to(torch.float64)
 
 
-def row_space_eligible(l1: float, constraints=None) -> bool:
-    return l1 == 0 and not constraints
+def row_space_eligible(l1: float, constraints=None, shift: bool = False) -> bool:
+    """``shift``: the data carries a normalization shift (``SegmentedGLMData.shift``), which the row-space Gram
+    matrices do not include."""
+    return l1 == 0 and not constraints and not shift
 
 
 # Size classes of the row-space batch: an entity with n_e rows joins the smallest class bound >= n_e and a class
