@@ -253,7 +253,8 @@ class EntityTronBatch:
                 ws_n = int(require_re_lib().pml_re_res_ws_doubles(max(n_cl_tickets, 1)))
                 self.res = dict(ent=idx.to(torch.int32).contiguous(), t0=t0.to(torch.int32).contiguous(),
                                 ws=torch.empty(ws_n, dtype=torch.float64, device=dev), grid=grid,
-                                n=int(idx.numel()), clusters=int((kk > 1).sum()), tickets=int(t0[-1]))
+                                n=int(idx.numel()), clusters=int((kk > 1).sum()), tickets=int(t0[-1]),
+                                kmax=int(kk.max()))
                 stream_sel = stream_sel & ~res
         for classes, sel, is_h in ((_HESS_CLASSES, hess, True), (_CLASSES, stream_sel, False)):
             cls = torch.searchsorted(torch.tensor(classes, device=dev), de)
@@ -271,6 +272,11 @@ class EntityTronBatch:
         solution, or zeros the first time). ``offsets``: per batch row."""
         from ..ops.native import re_tron_csr
         dev = self.y.device
+        if self.res is not None and self.res["grid"] < self.res["kmax"]:
+            # the members of a cluster meet at a barrier: with fewer workgroups than members they would wait for
+            # one another until the kernel's timeout
+            raise ValueError(f"register-resident launch: a grid of {self.res['grid']} workgroups cannot hold a "
+                             f"cluster of {self.res['kmax']}")
         if W0 is None:
             W0 = self.W if self.W is not None else torch.zeros(int(self.col_ptr[-1]), dtype=torch.float64,
                                                                 device=dev)

@@ -5,7 +5,8 @@ oracle itself.
 The oracle is ``optimization/tron.py`` (the LIBLINEAR-semantics TRON of the reference, ``TRON.scala:80-340``) on
 ``TorchGLMData`` in float64, one entity at a time on its own projected rows
 (``SingleNodeOptimizationProblem.scala:85-103``). ``tests/test_re_reference_weights.py`` shows that it treats row
-weights as row multiplicities.
+weights as row multiplicities. For L-BFGS / OWL-QN the oracle is ``batched.batched_lbfgs`` in float64 on the CPU over
+the segmented coordinate (:func:`cpu_owlqn`), with the rows of the data permuted for its floor.
 """
 import numpy as np
 import scipy.sparse as sp
@@ -167,6 +168,69 @@ def cpu_tron(data, loss, l2, tol, max_iter, partial=None, w0=None, rows=None, mu
         full[feats] = w.numpy()
         out[e] = (full, int(opt.current.iter), opt.convergence_reason())
     return out
+
+
+LBFGS_TASKS = dict(TASKS, HINGE="SMOOTHED_HINGE_LOSS_LINEAR_SVM")
+
+
+def permuted_rows(data, perm_seed):
+    """``data`` with its rows in another order (labels, offsets, weights and ids move with them): every entity's
+    problem is the same, its sums run in another order."""
+    p = np.random.default_rng(perm_seed).permutation(data.n_rows)
+    return GameData(data.response[p], {"user": data.shards["user"].tocsr()[p]}, {"userId": data.id_tags["userId"][p]},
+                    offsets=data.offsets[p], weights=data.weights[p])
+
+
+def lbfgs_coordinate(data, loss, device, l1_weight=0.5, tol=0.0, max_iter=5):
+    """A segmented random-effect coordinate under L-BFGS with an L1 weight (the configuration that routes to the
+    fused OWL-QN on the GPU), over the rows of ``data``."""
+    from photon_ml_amd.algorithm.coordinates import RandomEffectCoordinate
+    from photon_ml_amd.data.random_effect import RandomEffectDataConfiguration
+    from photon_ml_amd.optimization.config import (GLMOptimizationConfiguration, OptimizerConfig,
+                                                   RegularizationContext)
+    cfg = GLMOptimizationConfiguration(OptimizerConfig("LBFGS", max_iter, tol), RegularizationContext("L1"), l1_weight)
+    return RandomEffectCoordinate("u", data, RandomEffectDataConfiguration("userId", "user"), cfg, LBFGS_TASKS[loss],
+                                  device=device, layout="segmented")
+
+
+def segmented_offsets(c, data):
+    """The base offsets of ``data`` per segmented row of the coordinate ``c`` (what an update without a partial
+    score puts into ``seg.o``)."""
+    off = torch.from_numpy(np.asarray(data.offsets, dtype=np.float64))
+    return off[c.dataset.seg_rows.cpu()].to(c.dataset.seg.y.device)
+
+
+def entity_coefficients(ds, W):
+    """``{entity id: coefficients over the global features}`` of a vector packed like the dataset's segmented
+    coefficients (``projection_keys_t``: entity * dim + feature)."""
+    keys = ds.projection_keys_t.cpu().numpy()
+    ptr = ds.seg.col_ptr.cpu().numpy()
+    W = W.detach().cpu().numpy()
+    out = {}
+    for i, e in enumerate(ds.entity_ids):
+        full = np.zeros(ds.dim)
+        full[keys[ptr[i]:ptr[i + 1]] % ds.dim] = W[ptr[i]:ptr[i + 1]]
+        out[e] = full
+    return out
+
+
+def cpu_owlqn(data, loss, l2, l1, tol, max_iter, m=10, perm_seed=None):
+    """The OWL-QN / L-BFGS oracle: ``batched.batched_lbfgs`` in float64 on the CPU over the segmented coordinate of
+    ``data`` (what ``RandomEffectCoordinate(device="cpu", layout="segmented")`` runs), cold, with ``m`` history
+    pairs. ``perm_seed`` permutes the rows of the data first (:func:`permuted_rows`): the same problems, summed in
+    another order. ``{entity id: (w over the global features, iterations, reason code)}``."""
+    from photon_ml_amd.optimization.batched import batched_lbfgs
+    if perm_seed is not None:
+        data = permuted_rows(data, perm_seed)
+    c = lbfgs_coordinate(data, loss, "cpu")
+    ds = c.dataset
+    seg = ds.seg
+    seg.o = segmented_offsets(c, data)
+    seg._dzz_key = None
+    res = batched_lbfgs(seg, c.loss, l2, torch.zeros(int(seg.col_ptr[-1]), dtype=torch.float64), tol, max_iter, m=m,
+                        l1=l1)
+    W = entity_coefficients(ds, res.W)
+    return {e: (W[e], int(res.iters[i]), int(res.reason[i])) for i, e in enumerate(ds.entity_ids)}
 
 
 def cpu_objective(data, loss, l2, W, partial=None, rows=None, mult=None):
