@@ -77,6 +77,13 @@ class GameScoringDriver(GameDriverBase):
                 info = os.path.join(re_dir, cid, "id-info")
                 if os.path.exists(info):
                     self._tags.append(open(info).read().split()[0])
+        # a matrix-factorization coordinate reads both of its id columns (matrix-factorization/<cid>/id-info)
+        mf_dir = os.path.join(a.model_input_directory, "matrix-factorization")
+        if os.path.isdir(mf_dir):
+            for cid in sorted(os.listdir(mf_dir)):
+                info = os.path.join(mf_dir, cid, "id-info")
+                if os.path.exists(info):
+                    self._tags.extend(open(info).read().split("\n")[:2])
         self._tags = sorted(set(self._tags))
         with Timed("Read data"):
             paths = resolve_paths(a.input_data_directories, a.input_data_date_range, a.input_data_days_range)

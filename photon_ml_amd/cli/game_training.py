@@ -275,6 +275,8 @@ class GameTrainingDriver(GameDriverBase):
         if missing:
             raise ValueError(f"Coordinates {missing} in the update sequence have no configuration")
         for cid, cc in self.coord_configs.items():
+            if cc.is_matrix_factorization:
+                continue                        # no feature shard
             if cc.data_configuration.feature_shard_id not in self.shard_configs:
                 raise ValueError(f"Coordinate {cid} uses undefined feature shard "
                                  f"{cc.data_configuration.feature_shard_id}")
@@ -284,8 +286,7 @@ class GameTrainingDriver(GameDriverBase):
             raise ValueError("coordinate descent iterations must be > 0")
 
     def id_tags(self):
-        return sorted({cc.data_configuration.random_effect_type for cc in self.coord_configs.values()
-                       if cc.is_random_effect})
+        return sorted({t for cc in self.coord_configs.values() for t in cc.id_tag_names})
 
     # ------------------------------------------------------------------------------------------------------
     def run(self) -> Dict[str, object]:
@@ -331,7 +332,8 @@ class GameTrainingDriver(GameDriverBase):
                 save_feature_summary(os.path.join(d, "part-00000.avro"), st, maps[sid])
 
         fe_shards = {self.coord_configs[cid].data_configuration.feature_shard_id for cid in self.update_sequence
-                     if not self.coord_configs[cid].is_random_effect}
+                     if not self.coord_configs[cid].is_random_effect
+                     and not self.coord_configs[cid].is_matrix_factorization}
         if a.data_summary_directory:
             with Timed("Calculate statistics for the feature shards no fixed effect trains on"):
                 for sid in self.shard_configs:

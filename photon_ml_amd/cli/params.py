@@ -16,7 +16,8 @@ import os
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Sequence
 
-from ..data.random_effect import FixedEffectDataConfiguration, RandomEffectDataConfiguration
+from ..data.random_effect import (FixedEffectDataConfiguration, MatrixFactorizationDataConfiguration,
+                                  RandomEffectDataConfiguration)
 from ..io.data_reader import FeatureShardConfiguration
 from ..optimization.config import (GLMOptimizationConfiguration, OptimizerConfig, OptimizerType, RegularizationContext,
                                    RegularizationType)
@@ -82,6 +83,20 @@ class CoordinateConfiguration:
     def is_random_effect(self) -> bool:
         return isinstance(self.data_configuration, RandomEffectDataConfiguration)
 
+    @property
+    def is_matrix_factorization(self) -> bool:
+        return isinstance(self.data_configuration, MatrixFactorizationDataConfiguration)
+
+    @property
+    def id_tag_names(self) -> List[str]:
+        """The id columns the coordinate reads (none for a fixed effect)."""
+        dc = self.data_configuration
+        if self.is_random_effect:
+            return [dc.random_effect_type]
+        if self.is_matrix_factorization:
+            return [dc.row_effect_type, dc.col_effect_type]
+        return []
+
     def expand_optimization_configurations(self) -> List[GLMOptimizationConfiguration]:
         """One config per λ, descending (CoordinateConfiguration.scala:71-78); NONE regularisation -> [0]."""
         oc = self.optimization_configuration
@@ -92,6 +107,8 @@ class CoordinateConfiguration:
 
 def parse_coordinate_configuration(s: str) -> Dict[str, CoordinateConfiguration]:
     kv = parse_kv(s)
+    if "latent.factors" in kv:
+        return _parse_mf_coordinate_configuration(kv, s)
     for req in ("name", "feature.shard", "optimizer", "max.iter", "tolerance"):
         if req not in kv:
             raise ValueError(f"coordinate configuration requires '{req}': {s}")
@@ -119,7 +136,61 @@ def parse_coordinate_configuration(s: str) -> Dict[str, CoordinateConfiguration]
     return {name: CoordinateConfiguration(dc, opt, weights)}
 
 
+def _optimization_of(kv: Dict[str, str]):
+    oc = OptimizerConfig(OptimizerType.parse(kv["optimizer"]), int(kv["max.iter"]), float(kv["tolerance"]))
+    reg = RegularizationType.parse(kv.get("regularization", "NONE"))
+    if reg == RegularizationType.ELASTIC_NET:
+        rc = RegularizationContext(reg, float(kv["reg.alpha"]) if "reg.alpha" in kv else None)
+    else:
+        rc = RegularizationContext(reg)
+    weights = [float(x) for x in kv["reg.weights"].split(SECONDARY)] if "reg.weights" in kv else []
+    return oc, rc, weights
+
+
+def _parse_mf_coordinate_configuration(kv: Dict[str, str], s: str) -> Dict[str, CoordinateConfiguration]:
+    """A configuration with ``latent.factors`` is a matrix-factorization coordinate: ``row.effect.type`` and
+    ``col.effect.type`` name its id columns, it has no ``feature.shard``; ``mf.alternations``, ``mf.init.std`` and
+    ``mf.seed`` are optional. What the coordinate cannot combine with (optimizer, regularization, down-sampling) is
+    refused by the coordinate itself, with its name, before any training."""
+    for req in ("name", "row.effect.type", "col.effect.type", "optimizer", "max.iter", "tolerance"):
+        if req not in kv:
+            raise ValueError(f"matrix-factorization coordinate configuration requires '{req}': {s}")
+    for bad in ("feature.shard", "random.effect.type"):
+        if bad in kv:
+            raise ValueError(f"matrix-factorization coordinate configuration takes no '{bad}': {s}")
+    oc, rc, weights = _optimization_of(kv)
+    extra = {}
+    if "mf.alternations" in kv:
+        extra["alternations"] = int(kv["mf.alternations"])
+    if "mf.init.std" in kv:
+        extra["init_std"] = float(kv["mf.init.std"])
+    if "mf.seed" in kv:
+        extra["seed"] = int(kv["mf.seed"])
+    dc = MatrixFactorizationDataConfiguration(kv["row.effect.type"], kv["col.effect.type"], int(kv["latent.factors"]),
+                                              **extra)
+    opt = GLMOptimizationConfiguration(oc, rc, 0.0, float(kv.get("down.sampling.rate", "1.0")))
+    return {kv["name"]: CoordinateConfiguration(dc, opt, weights)}
+
+
+def _mf_coordinate_configuration_to_string(name: str, cc: CoordinateConfiguration) -> str:
+    dc, oc = cc.data_configuration, cc.optimization_configuration
+    parts = [f"name={name}", f"row.effect.type={dc.row_effect_type}", f"col.effect.type={dc.col_effect_type}",
+             f"latent.factors={dc.num_factors}", f"optimizer={oc.optimizer_config.optimizer_type.value}",
+             f"max.iter={oc.optimizer_config.maximum_iterations}", f"tolerance={oc.optimizer_config.tolerance}",
+             f"regularization={oc.regularization_context.regularization_type.value}"]
+    if oc.regularization_context.elastic_net_param is not None:
+        parts.append(f"reg.alpha={oc.regularization_context.elastic_net_param}")
+    if cc.regularization_weights:
+        parts.append("reg.weights=" + SECONDARY.join(str(w) for w in cc.regularization_weights))
+    parts += [f"mf.alternations={dc.alternations}", f"mf.init.std={dc.init_std!r}", f"mf.seed={dc.seed}"]
+    if oc.down_sampling_rate != 1.0:
+        parts.append(f"down.sampling.rate={oc.down_sampling_rate}")
+    return ",".join(parts)
+
+
 def coordinate_configuration_to_string(name: str, cc: CoordinateConfiguration) -> str:
+    if cc.is_matrix_factorization:
+        return _mf_coordinate_configuration_to_string(name, cc)
     dc, oc = cc.data_configuration, cc.optimization_configuration
     parts = [f"name={name}", f"feature.shard={dc.feature_shard_id}", f"min.partitions={dc.min_partitions}",
              f"optimizer={oc.optimizer_config.optimizer_type.value}",

@@ -56,6 +56,33 @@ class FixedEffectDataConfiguration:
     min_partitions: int = 1
 
 
+@dataclass
+class MatrixFactorizationDataConfiguration:
+    """A matrix-factorization coordinate: score ``u_i . v_j`` for the row-side entity i (id tag ``row_effect_type``)
+    and the column-side entity j (``col_effect_type``) of a sample, ``num_factors`` latent factors per entity
+    (``algorithm/matrix_factorization.py`` checks 1..32 with the coordinate's name). It has no feature shard.
+    ``alternations``: rounds of (row half, column half) per coordinate update; ``init_std`` / ``seed``: the column
+    factors start as N(0, init_std^2) draws of ``numpy.random.default_rng(seed)`` in sorted-id order."""
+    row_effect_type: str
+    col_effect_type: str
+    num_factors: int
+    alternations: int = 1
+    init_std: float = 0.1
+    seed: int = 20260719
+
+    def __post_init__(self):
+        self.num_factors = int(self.num_factors)
+        self.alternations = int(self.alternations)
+        self.init_std = float(self.init_std)
+        self.seed = int(self.seed)
+        if self.alternations < 1:
+            raise ValueError("matrix factorization needs at least one alternation per update")
+        if not self.init_std > 0:
+            raise ValueError("matrix factorization init_std must be positive (U = V = 0 is a stationary point)")
+        if self.seed < 0:
+            raise ValueError("matrix factorization seed must be non-negative")
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # Reservoir key (RandomEffectDataSet.scala:361-367): (byteswap64(reType.hashCode) ^ byteswap64(uid)).hashCode()
 def java_string_hash(s: str) -> int:

@@ -29,7 +29,8 @@ from ..algorithm.coordinates import FixedEffectCoordinate, RandomEffectCoordinat
 from ..constants import RANDOM_SEED, TaskType, VarianceComputationType
 from ..data.game_data import GameData
 from ..data.matrix import LabeledData
-from ..data.random_effect import FixedEffectDataConfiguration, RandomEffectDataConfiguration
+from ..data.random_effect import (FixedEffectDataConfiguration, MatrixFactorizationDataConfiguration,
+                                  RandomEffectDataConfiguration)
 from ..evaluation.evaluators import (build_evaluator, default_validation_evaluator, parse_evaluator_type,
                                      training_loss_evaluator_type)
 from ..models.game import GameModel
@@ -219,6 +220,8 @@ class GameEstimator:
     def _prior_for(self, cid: str, random_effect: bool):
         from ..models.game import FixedEffectModel, RandomEffectModel
         m = None if self.prior_model is None else self.prior_model.get(cid)
+        if isinstance(self.coordinate_data_configurations.get(cid), MatrixFactorizationDataConfiguration):
+            return m       # the coordinate refuses any prior, with its name
         if m is not None and not isinstance(m, RandomEffectModel if random_effect else FixedEffectModel):
             raise ValueError(f"coordinate {cid}: the prior model holds a {type(m).__name__} for it")
         return m
@@ -252,10 +255,12 @@ class GameEstimator:
         # the first random-effect shard built after a fixed-effect coordinate is copied to the device while the GPU
         # builds the fixed-effect layout (a host CSR shard no fixed effect reads; GPU only)
         fe_shards = {dc.feature_shard_id for dc in self.coordinate_data_configurations.values()
-                     if not isinstance(dc, RandomEffectDataConfiguration)}
+                     if isinstance(dc, FixedEffectDataConfiguration)}
         seen_fe = False
         for cid in seq:
             dc = self.coordinate_data_configurations[cid]
+            if isinstance(dc, MatrixFactorizationDataConfiguration):
+                continue                       # no feature shard
             if not isinstance(dc, RandomEffectDataConfiguration):
                 seen_fe = True
             elif seen_fe and dc.feature_shard_id not in fe_shards:
@@ -264,7 +269,15 @@ class GameEstimator:
         for cid in seq:
             dc = self.coordinate_data_configurations[cid]
             oc = first_cfg[cid]
-            if isinstance(dc, RandomEffectDataConfiguration):
+            if isinstance(dc, MatrixFactorizationDataConfiguration):
+                from ..algorithm.matrix_factorization import MatrixFactorizationCoordinate
+                if self.compute_variance or cid in self.coordinate_normalization_contexts \
+                        or self.normalization_type != NormalizationType.NONE:
+                    log.info("coordinate %s: normalization and variance settings do not apply to matrix factorization "
+                             "(no features, no variances)", cid)
+                coords[cid] = MatrixFactorizationCoordinate(cid, data, dc, oc, self.training_task, self.device,
+                                                            prior=self._prior_for(cid, False))
+            elif isinstance(dc, RandomEffectDataConfiguration):
                 cls = ShardedRandomEffectCoordinate if is_dist() else RandomEffectCoordinate
                 coords[cid] = cls(cid, data, dc, oc, self.training_task, self.variance_computation_type, self.device,
                                   prior=self._prior_for(cid, True),

@@ -78,7 +78,7 @@ SCORING_RESULT = {
 
 LATENT_FACTOR = {
     "type": "record", "name": "LatentFactorAvro", "namespace": "com.linkedin.photon.avro.generated",
-    "doc": "latent factor of a matrix-factorization model (schema parity only: the reference has no MF training)",
+    "doc": "latent factor of one entity of a matrix-factorization model",
     "fields": [{"name": "effectId", "type": "string"},
                {"name": "latentFactor", "type": {"type": "array", "items": "double"}}],
 }

@@ -25,9 +25,9 @@ import numpy as np
 import torch
 
 from ..constants import MODEL_SPARSITY_THRESHOLD, TaskType, split_feature_key, feature_key
-from ..models.game import FixedEffectModel, GameModel, RandomEffectModel
+from ..models.game import FixedEffectModel, GameModel, MatrixFactorizationModel, RandomEffectModel
 from ..models.glm import FQCN, LOSS_FQCN, Coefficients, model_for_task, task_from_model_class
-from .avro import BAYESIAN_LINEAR_MODEL, read_records, write_records, avro_files
+from .avro import BAYESIAN_LINEAR_MODEL, LATENT_FACTOR, read_records, write_records, avro_files
 from .index_map import IndexMap
 
 # random-effect models are written by the native encoder (write_linear_models); 0: per-record Python dictionaries
@@ -41,6 +41,9 @@ BLOCK_BYTES = 1 << 20
 
 FIXED_EFFECT = "fixed-effect"
 RANDOM_EFFECT = "random-effect"
+MATRIX_FACTORIZATION = "matrix-factorization"
+ROW_LATENT_FACTORS = "row-latent-factors"
+COL_LATENT_FACTORS = "col-latent-factors"
 ID_INFO = "id-info"
 COEFFICIENTS = "coefficients"
 METADATA = "model-metadata.json"
@@ -217,6 +220,17 @@ def save_game_model(model: GameModel, out_dir: str, index_maps: Dict[str, IndexM
                 write_records(path, BAYESIAN_LINEAR_MODEL, recs, codec=MODEL_CODEC,
                               block_records=block_records(len(recs), sum(len(r["means"]) for r in recs),
                                                           m.variances is not None))
+        elif isinstance(m, MatrixFactorizationModel):
+            if not lead:
+                continue
+            d = os.path.join(out_dir, MATRIX_FACTORIZATION, cid)
+            os.makedirs(d, exist_ok=True)
+            with open(os.path.join(d, ID_INFO), "w") as f:
+                f.write(f"{m.row_effect_type}\n{m.col_effect_type}\n{m.num_factors}\n")
+            for sub, ids, tab in ((ROW_LATENT_FACTORS, m.row_ids, m.U), (COL_LATENT_FACTORS, m.col_ids, m.V)):
+                tab = tab.detach().cpu().numpy()
+                recs = [{"effectId": str(e), "latentFactor": [float(x) for x in row]} for e, row in zip(ids, tab)]
+                write_records(os.path.join(d, sub, "part-00000.avro"), LATENT_FACTOR, recs, codec=MODEL_CODEC)
         else:
             raise TypeError(f"unknown model type {type(m)}")
 
@@ -280,6 +294,26 @@ def load_game_model(model_dir: str, index_maps: Dict[str, IndexMap]) -> GameMode
                                             np.concatenate(keys) if keys else np.zeros(0, np.int64),
                                             np.concatenate(vals) if vals else np.zeros(0),
                                             np.concatenate(vars_) if vars_ and len(vars_) == len(vals) else None)
+    mf_root = os.path.join(model_dir, MATRIX_FACTORIZATION)
+    if os.path.isdir(mf_root):
+        for cid in sorted(os.listdir(mf_root)):
+            d = os.path.join(mf_root, cid)
+            info = open(os.path.join(d, ID_INFO)).read().split("\n")
+            row_type, col_type, k = info[0], info[1], int(info[2])
+            tabs = []
+            for sub in (ROW_LATENT_FACTORS, COL_LATENT_FACTORS):
+                recs = []
+                for fpath in avro_files(os.path.join(d, sub)):
+                    recs.extend(read_records(fpath)[1])
+                recs.sort(key=lambda r: str(r["effectId"]))
+                ids = np.array([str(r["effectId"]) for r in recs], dtype=str)
+                tab = np.array([r["latentFactor"] for r in recs], dtype=np.float64).reshape(len(recs), k)
+                order = np.argsort(ids, kind="stable")        # numpy's string order, as the coordinate's id tables
+                tabs.append((ids[order], tab[order]))
+            if task == TaskType.NONE:
+                raise ValueError(f"matrix-factorization model {cid}: {METADATA} with the model type is required")
+            models[cid] = MatrixFactorizationModel(row_type, col_type, task, tabs[0][0], tabs[1][0],
+                                                   torch.from_numpy(tabs[0][1]), torch.from_numpy(tabs[1][1]))
     if not models:
         raise ValueError(f"no model found under {model_dir}")
     return GameModel(models)

@@ -314,6 +314,95 @@ class RandomEffectModel:
                 f"entities={self.n_entities}, nnz={self.nnz})")
 
 
+def _id_keys(ids) -> np.ndarray:
+    """Entity ids as comparable keys (object arrays as strings, like ``RandomEffectModel.entity_index``)."""
+    ids = np.asarray(ids)
+    return ids.astype(str) if ids.dtype == object else ids
+
+
+def entity_codes(sorted_ids: np.ndarray, ids) -> np.ndarray:
+    """Position of every id of ``ids`` in the sorted table ``sorted_ids`` (-1: absent), int32."""
+    ids = _id_keys(ids)
+    n = len(sorted_ids)
+    if n == 0:
+        return np.full(len(ids), -1, dtype=np.int32)
+    if sorted_ids.dtype.kind in "US" and ids.dtype.kind not in "US":
+        ids = ids.astype(str)
+    pos = np.searchsorted(sorted_ids, ids)
+    pos_c = np.minimum(pos, n - 1)
+    return np.where((pos < n) & (sorted_ids[pos_c] == ids), pos, -1).astype(np.int32)
+
+
+class MatrixFactorizationModel:
+    """Latent factors of one matrix-factorization coordinate: ``U [I, K]`` for the row-side entities ``row_ids``
+    (id tag ``row_effect_type``) and ``V [J, K]`` for the column-side entities ``col_ids`` (``col_effect_type``),
+    both id tables sorted. A sample scores ``u_i . v_j``; a sample whose row or column entity is not in the model
+    scores 0 (the random-effect convention for unseen entities). The factors are fp64 torch tensors wherever the
+    solver left them (host or device)."""
+
+    def __init__(self, row_effect_type: str, col_effect_type: str, task, row_ids, col_ids, U, V):
+        self.row_effect_type = row_effect_type
+        self.col_effect_type = col_effect_type
+        self._task = TaskType.parse(task)
+        self.row_ids, self.col_ids = _id_keys(row_ids), _id_keys(col_ids)
+        as_t = lambda a: a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a, dtype=np.float64))
+        self.U, self.V = as_t(U).to(torch.float64), as_t(V).to(torch.float64)
+        if self.U.dim() != 2 or self.V.dim() != 2 or self.U.shape[1] != self.V.shape[1]:
+            raise ValueError(f"factor tables of shapes {tuple(self.U.shape)} and {tuple(self.V.shape)}")
+        if self.U.shape[0] != len(self.row_ids) or self.V.shape[0] != len(self.col_ids):
+            raise ValueError("factor tables and id tables differ in length")
+        for ids in (self.row_ids, self.col_ids):
+            if len(ids) > 1 and not bool(np.all(ids[1:] > ids[:-1])):
+                raise ValueError("matrix-factorization id tables must be sorted and distinct")
+
+    @property
+    def task(self) -> TaskType:
+        return self._task
+
+    @property
+    def num_factors(self) -> int:
+        return int(self.U.shape[1])
+
+    def codes(self, data, dev) -> tuple:
+        """(row-entity, column-entity) code of every sample row (-1: not in the model), int32 on ``dev``; cached on
+        the data object for these id tables."""
+        cache = data.__dict__.setdefault("_pml_mf_cache", {})
+        key = (self.row_effect_type, self.col_effect_type, id(self.row_ids), id(self.col_ids), str(dev))
+        hit = cache.get(key)
+        if hit is None or hit[0] is not self.row_ids or hit[1] is not self.col_ids:
+            for tag in (self.row_effect_type, self.col_effect_type):
+                if tag not in data.id_tags:
+                    raise KeyError(f"id tag {tag} not present in the data (have {sorted(data.id_tags)})")
+            a = entity_codes(self.row_ids, data.id_tags[self.row_effect_type])
+            b = entity_codes(self.col_ids, data.id_tags[self.col_effect_type])
+            hit = (self.row_ids, self.col_ids, torch.from_numpy(a).to(dev), torch.from_numpy(b).to(dev))
+            cache[key] = hit
+        return hit[2], hit[3]
+
+    def score(self, data, device="cpu") -> torch.Tensor:
+        dev = torch.device(device)
+        a, b = self.codes(data, dev)
+        return pair_scores(self.U.to(dev), self.V.to(dev), a, b)
+
+    def __repr__(self):
+        return (f"MatrixFactorizationModel(row={self.row_effect_type}, col={self.col_effect_type}, "
+                f"entities={len(self.row_ids)}x{len(self.col_ids)}, factors={self.num_factors})")
+
+
+def pair_scores(U: torch.Tensor, V: torch.Tensor, a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """``U[a_r] . V[b_r]`` per row, 0 where either code is -1: ``mf_score_kernel`` on a GPU, fp64 torch on the host."""
+    if U.is_cuda:
+        from ..ops.native import mf_score
+        return mf_score(a.to(torch.int32).contiguous(), b.to(torch.int32).contiguous(), U.contiguous(),
+                        V.contiguous())
+    ok = (a >= 0) & (b >= 0)
+    al, bl = a.clamp(min=0).long(), b.clamp(min=0).long()
+    if U.shape[0] == 0 or V.shape[0] == 0:
+        return torch.zeros(a.numel(), dtype=torch.float64)
+    s = (U[al] * V[bl]).sum(1)
+    return torch.where(ok, s, torch.zeros_like(s))
+
+
 class GameModel:
     """Ordered map coordinate id -> model; all sub-models must share one task type."""
 

@@ -33,6 +33,7 @@ HIP_SOURCES = {
     "glm": PKG / "ops" / "csrc" / "glm_kernels.hip",
     "game": PKG / "ops" / "csrc" / "game_kernels.hip",
     "re": PKG / "ops" / "csrc" / "re_kernels.hip",
+    "mf": PKG / "ops" / "csrc" / "mf_kernels.hip",
 }
 CPP_SOURCES = {
     "avro": PKG / "io" / "csrc" / "avro_codec.cpp",

@@ -1876,6 +1876,106 @@ def re_tron_res(task_ent, task_t0, ws, grid: int, row_ptr, col_ptr, nip, lcol, v
     return err
 
 
+def mf_lib() -> Optional[ctypes.CDLL]:
+    """Matrix-factorization kernels (``ops/csrc/mf_kernels.hip``): the gathering per-entity TRON and the u.v scorer."""
+    lib = _load("mf")
+    if lib is not None and not getattr(lib, "_pml_typed", False):
+        lib.pml_mf_tron.argtypes = ([c_void_p, c_int] + [c_void_p] * 7 + [ctypes.c_longlong] + [c_void_p] * 6
+                                    + [c_int, c_int, c_double, c_double, c_int, c_int, c_int, c_void_p])
+        lib.pml_mf_tron.restype = c_int
+        lib.pml_mf_tron_smem.argtypes = [c_int]
+        lib.pml_mf_tron_smem.restype = ctypes.c_size_t
+        lib.pml_mf_score.argtypes = [ctypes.c_longlong, c_int] + [c_void_p] * 6
+        lib.pml_mf_score.restype = c_int
+        lib._pml_typed = True
+    return lib
+
+
+def require_mf_lib() -> ctypes.CDLL:
+    lib = mf_lib()
+    if lib is None:
+        raise RuntimeError(
+            f"native matrix-factorization kernel library missing ({lib_path('hip', 'mf')}); run python -m "
+            f"photon_ml_amd.ops.build")
+    return lib
+
+
+MF_MAX_FACTORS = 32      # mf_tron_kernel<T>: T in {1, 2} pads K to 16 / 32
+
+
+def check_mf_tron_inputs(order: torch.Tensor, row_ptr: torch.Tensor, oid: torch.Tensor, other: torch.Tensor,
+                         n_rows: int, K: int) -> None:
+    """Host-side check of everything ``mf_tron_kernel`` indexes by (``PML_CHECK_KERNEL_INPUTS=1``): ``row_ptr``
+    monotone from 0 to the row count, every launched entity inside it, every ``oid`` a row of the other side's
+    table. Raises ValueError; nothing is launched."""
+    n_ent = int(row_ptr.numel()) - 1
+    if n_ent < 0 or int(row_ptr[0]) != 0 or int(row_ptr[-1]) != n_rows:
+        raise ValueError(f"mf_tron: row_ptr must run from 0 to the {n_rows} rows")
+    if n_ent and bool((row_ptr[1:] < row_ptr[:-1]).any()):
+        raise ValueError("mf_tron: row_ptr is not monotone")
+    if order.numel() and (int(order.min()) < 0 or int(order.max()) >= n_ent):
+        raise ValueError("mf_tron: launch order out of range")
+    J = other.numel() // K
+    if oid.numel() and (int(oid.min()) < 0 or int(oid.max()) >= J):
+        raise ValueError(f"mf_tron: other-side code outside the table of {J} entities")
+
+
+def mf_tron(order, row_ptr, oid, other, y, off, wt, scr, W, f, iters, reason, zout, K: int, loss_id: int, l2: float,
+            tol: float, max_iter: int, max_fail: int = 5, max_cg: int = 20,
+            npass: Optional[torch.Tensor] = None) -> None:
+    """Fused per-entity TRON of one matrix-factorization half-update (``mf_tron_kernel``, one wave per entity).
+    Entity ``e`` of ``order`` (int32) owns the sorted rows ``row_ptr[e]:row_ptr[e+1]`` (int64) and the factors
+    ``W[e*K:(e+1)*K]`` (fp64; in: warm start, out: solution); the feature vector of row r is ``other[oid[r]]``
+    (``oid`` int32 per sorted row, ``other`` fp64 [J, K], 1 <= K <= 32). ``y`` / ``off`` / ``wt`` per sorted row;
+    ``scr`` fp64 scratch of 2 x rows; outputs ``f`` / ``iters`` / ``reason`` per entity and ``zout`` (the margins
+    ``u . v`` per sorted row, no offset); ``npass`` (optional int32 per entity): row passes run. Device only; in
+    place, nothing returned."""
+    K = int(K)
+    if not 1 <= K <= MF_MAX_FACTORS:
+        raise ValueError(f"mf_tron: {K} factors outside 1..{MF_MAX_FACTORS}")
+    lib = require_mf_lib()
+    n_rows = int(y.numel())
+    n_ent = int(row_ptr.numel()) - 1
+    for t in (order, row_ptr, oid, other, y, off, wt, scr, W, f, iters, reason, zout):
+        assert t.is_cuda and t.is_contiguous() and t.device == W.device
+    assert order.dtype == oid.dtype == iters.dtype == reason.dtype == torch.int32 and row_ptr.dtype == torch.int64
+    assert all(t.dtype == torch.float64 for t in (other, y, off, wt, scr, W, f, zout))
+    if (oid.numel() != n_rows or off.numel() != n_rows or wt.numel() != n_rows or zout.numel() != n_rows
+            or scr.numel() < 2 * n_rows):
+        raise ValueError(f"mf_tron: per-row arrays / scratch do not match the {n_rows} rows")
+    if n_ent < 0 or W.numel() != n_ent * K or f.numel() != n_ent or iters.numel() != n_ent \
+            or reason.numel() != n_ent or other.numel() % K:
+        raise ValueError(f"mf_tron: factor tables / outputs do not match {n_ent} entities of {K} factors")
+    if npass is not None:
+        assert npass.is_cuda and npass.dtype == torch.int32 and npass.numel() == n_ent
+    if os.environ.get("PML_CHECK_KERNEL_INPUTS", "0") == "1":
+        check_mf_tron_inputs(order, row_ptr, oid, other, n_rows, K)
+    check(lib.pml_mf_tron(order.data_ptr(), int(order.numel()), row_ptr.data_ptr(), oid.data_ptr(), other.data_ptr(),
+                          y.data_ptr(), off.data_ptr(), wt.data_ptr(), scr.data_ptr(), n_rows, W.data_ptr(),
+                          f.data_ptr(), iters.data_ptr(), reason.data_ptr(), zout.data_ptr(),
+                          None if npass is None else npass.data_ptr(), K, int(loss_id), float(l2), float(tol),
+                          int(max_iter), int(max_fail), int(max_cg), stream_handle(W.device)), "mf_tron")
+
+
+def mf_score(ra: torch.Tensor, cb: torch.Tensor, U: torch.Tensor, V: torch.Tensor) -> torch.Tensor:
+    """``s_r = U[ra_r] . V[cb_r]`` per row, 0 where either code is -1 (``mf_score_kernel``). ``ra`` / ``cb`` int32
+    per row, ``U`` [I, K] / ``V`` [J, K] fp64 on one device."""
+    lib = require_mf_lib()
+    for t in (ra, cb, U, V):
+        assert t.is_cuda and t.is_contiguous() and t.device == U.device
+    assert ra.dtype == cb.dtype == torch.int32 and U.dtype == V.dtype == torch.float64
+    if U.dim() != 2 or V.dim() != 2 or U.shape[1] != V.shape[1] or U.shape[1] < 1 or ra.numel() != cb.numel():
+        raise ValueError(f"mf_score: factor tables {tuple(U.shape)} / {tuple(V.shape)} or code arrays do not match")
+    n = int(ra.numel())
+    if os.environ.get("PML_CHECK_KERNEL_INPUTS", "0") == "1" and n:
+        if int(ra.min()) < -1 or int(ra.max()) >= U.shape[0] or int(cb.min()) < -1 or int(cb.max()) >= V.shape[0]:
+            raise ValueError("mf_score: entity code outside its factor table")
+    out = torch.empty(n, dtype=torch.float64, device=U.device)
+    check(lib.pml_mf_score(n, int(U.shape[1]), ra.data_ptr(), cb.data_ptr(), U.data_ptr(), V.data_ptr(),
+                           out.data_ptr(), stream_handle(U.device)), "mf_score")
+    return out
+
+
 def check(rc: int, what: str):
     if rc != 0:
         raise RuntimeError(f"{what} failed with HIP error {rc}")

@@ -81,7 +81,7 @@ def _array_to_strings(a: np.ndarray, n: int, version: Optional[int] = FORMAT_VER
 
 
 def game_model_to_arrays(model, prefix: str) -> Tuple[Dict[str, np.ndarray], dict]:
-    from ..models.game import FixedEffectModel, RandomEffectModel
+    from ..models.game import FixedEffectModel, MatrixFactorizationModel, RandomEffectModel
     arrays, meta = {}, {"coordinates": []}
     for cid, m in model:
         key = f"{prefix}{cid}"
@@ -101,6 +101,14 @@ def game_model_to_arrays(model, prefix: str) -> Tuple[Dict[str, np.ndarray], dic
             meta["coordinates"].append({"id": cid, "kind": "random", "shard": m.feature_shard_id,
                                         "re_type": m.random_effect_type, "task": m.task.value, "dim": m.dim,
                                         "n_entities": int(m.n_entities)})
+        elif isinstance(m, MatrixFactorizationModel):
+            arrays[key + ".U"] = m.U.detach().cpu().numpy().astype(np.float64)
+            arrays[key + ".V"] = m.V.detach().cpu().numpy().astype(np.float64)
+            arrays[key + ".row_ids"] = _strings_to_array(m.row_ids)
+            arrays[key + ".col_ids"] = _strings_to_array(m.col_ids)
+            meta["coordinates"].append({"id": cid, "kind": "mf", "row_type": m.row_effect_type,
+                                        "col_type": m.col_effect_type, "task": m.task.value,
+                                        "n_rows": len(m.row_ids), "n_cols": len(m.col_ids)})
         else:
             raise TypeError(type(m))
     return arrays, meta
@@ -108,7 +116,7 @@ def game_model_to_arrays(model, prefix: str) -> Tuple[Dict[str, np.ndarray], dic
 
 def game_model_from_arrays(arrays: Dict[str, np.ndarray], meta: dict, prefix: str,
                            version: Optional[int] = FORMAT_VERSION):
-    from ..models.game import FixedEffectModel, GameModel, RandomEffectModel
+    from ..models.game import FixedEffectModel, GameModel, MatrixFactorizationModel, RandomEffectModel
     from ..models.glm import Coefficients, model_for_task
     models = OrderedDict()
     for c in meta["coordinates"]:
@@ -119,6 +127,12 @@ def game_model_from_arrays(arrays: Dict[str, np.ndarray], meta: dict, prefix: st
             coef = Coefficients(torch.from_numpy(arrays[key + ".means"].copy()),
                                 None if var is None else torch.from_numpy(var.copy()))
             models[c["id"]] = FixedEffectModel(model_for_task(task, coef), c["shard"])
+        elif c["kind"] == "mf":
+            rows = _array_to_strings(arrays[key + ".row_ids"], c["n_rows"], version).astype(str)
+            cols = _array_to_strings(arrays[key + ".col_ids"], c["n_cols"], version).astype(str)
+            models[c["id"]] = MatrixFactorizationModel(c["row_type"], c["col_type"], task, rows, cols,
+                                                       torch.from_numpy(arrays[key + ".U"].copy()),
+                                                       torch.from_numpy(arrays[key + ".V"].copy()))
         else:
             ents = _array_to_strings(arrays[key + ".entities"], c["n_entities"], version)
             models[c["id"]] = RandomEffectModel(c["re_type"], c["shard"], task, ents, c["dim"],
