@@ -25,95 +25,10 @@
 //
 // Built with: hipcc --offload-arch=gfx950 -O3 -shared -fPIC (photon_ml_amd/ops/build.py). C ABI, ctypes.
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-// Build id (photon_ml_amd/ops/build.py: content hash of the sources + compile command, -DPML_BUILD_ID=...): the
-// loaders compare it with the tree's sources and refuse a stale library.
-#ifndef PML_BUILD_ID
-#define PML_BUILD_ID "unstamped-build!"
-#endif
-__attribute__((used)) static const char pml_build_stamp[] = "PML_BUILD_ID=" PML_BUILD_ID;
-
-#define LAUNCH_CHECK()                                         \
-  do {                                                         \
-    hipError_t e_ = hipGetLastError();                         \
-    if (e_ != hipSuccess) return (int)e_;                      \
-  } while (0)
+#include "tron_core.h"
 
 #define RE_NW 4                 // waves per workgroup (one entity)
 #define RE_THREADS (RE_NW * 64)
-
-enum { LOSS_LOGISTIC = 0, LOSS_POISSON = 1, LOSS_SQUARED = 2, LOSS_HINGE = 3 };
-
-template <int LOSS>
-__device__ __forceinline__ void loss_t(double z, double y, double& l, double& dl, double& d2) {
-  if constexpr (LOSS == LOSS_LOGISTIC) {
-    // one exp, one log1p, one reciprocal, no branches (as pointwise_loss in glm_kernels.hip):
-    // e = exp(-|z|) serves the sigmoid and log(1 + exp(+-z)) = max(+-z, 0) + log1p(e)
-    const double e = exp(-fabs(z));
-    const double lp = log1p(e);
-    const double r = 1.0 / (1.0 + e);
-    const double s = z >= 0.0 ? r : e * r;
-    const bool pos = y > 0.5;
-    const double zz = pos ? -z : z;
-    l = (zz > 0.0 ? zz : 0.0) + lp;
-    dl = pos ? s - 1.0 : s;
-    d2 = s * (1.0 - s);
-  } else if constexpr (LOSS == LOSS_POISSON) {
-    const double e = exp(z);
-    l = e - y * z; dl = e - y; d2 = e;
-  } else if constexpr (LOSS == LOSS_HINGE) {
-    // Rennie & Srebro smoothed hinge (function/losses.py, pointwise_loss in glm_kernels.hip): once differentiable
-    const double yy = y < 0.5 ? -1.0 : 1.0;
-    const double t = yy * z;
-    l = t <= 0.0 ? 0.5 - t : (t < 1.0 ? 0.5 * (1.0 - t) * (1.0 - t) : 0.0);
-    dl = (t < 0.0 ? -1.0 : (t < 1.0 ? t - 1.0 : 0.0)) * yy;
-    d2 = 0.0;
-  } else {
-    const double d = z - y;
-    l = 0.5 * d * d; dl = d; d2 = 1.0;
-  }
-}
-
-// weight x per-row term with an exact 0 for zero-weight rows whatever the term (wx in glm_kernels.hip): a
-// zero-weight row whose exp overflowed (a partial score, an overshooting trial step) must not turn 0 x inf into NaN
-__device__ __forceinline__ double wx(double w, double x) { return w != 0.0 ? w * x : 0.0; }
-
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {
-  const long long b = __builtin_bit_cast(long long, v);
-  const int lo = __builtin_amdgcn_update_dpp(0, (int)b, CTRL, 0xF, 0xF, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, (int)(b >> 32), CTRL, 0xF, 0xF, true);
-  return __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned int)lo);
-}
-
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-  const long long b = __builtin_bit_cast(long long, v);
-  const int lo = __builtin_amdgcn_readlane((int)b, l);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
-  return __builtin_bit_cast(double, ((long long)hi << 32) | (long long)(unsigned int)lo);
-}
-
-// Sum over the 64 lanes of a wave, returned (bitwise identical) in every lane: DPP butterflies inside each
-// 16-lane row (every lane then holds its row's sum), then the four row sums in a fixed order.
-__device__ __forceinline__ double wave_total(double v) {
-  v += dpp_f64<0xB1>(v);    // quad_perm [1,0,3,2]
-  v += dpp_f64<0x4E>(v);    // quad_perm [2,3,0,1]
-  v += dpp_f64<0x141>(v);   // row_half_mirror
-  v += dpp_f64<0x140>(v);   // row_mirror
-  return (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
-}
-
-// A workgroup-uniform value re-tagged as wave-uniform (readfirstlane): it is held in SGPRs, not VGPRs.
-__device__ __forceinline__ long long uniform_i64(long long v) {
-  const int lo = __builtin_amdgcn_readfirstlane((int)v);
-  const int hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
-  return ((long long)hi << 32) | (long long)(unsigned int)lo;
-}
-__device__ __forceinline__ double uniform_f64(double v) {
-  return __builtin_bit_cast(double, uniform_i64(__builtin_bit_cast(long long, v)));
-}
 
 // Workgroup sums of K values (K <= 8), in every thread. ``red`` holds two [RE_NW][8] slots used alternately,
 // so one barrier per call suffices: a slot is rewritten only two calls later, after every thread has passed
@@ -166,22 +81,6 @@ struct ReTronArgs {
   const double* nc;          // re_tron_csr_kernel<LOSS, true>: shift c = f s per coefficient (packed like W)
   const int* ni0;            // re_tron_csr_kernel<LOSS, true>: entity-local intercept column per entity (c[i0] = 0)
 };
-
-// Loads through the global address space: a generic pointer read through the kernel-argument struct becomes a FLAT
-// load, which also counts in lgkmcnt -- every LDS wait would then wait for it too.
-template <typename T>
-__device__ __forceinline__ T gld(const T* p) {
-  return *(const __attribute__((address_space(1))) T*)p;
-}
-
-// Sum over the 16 lanes of a DPP row, in every lane of the row (fixed-order butterflies: deterministic).
-__device__ __forceinline__ double row16_total(double v) {
-  v += dpp_f64<0xB1>(v);    // quad_perm [1,0,3,2]
-  v += dpp_f64<0x4E>(v);    // quad_perm [2,3,0,1]
-  v += dpp_f64<0x141>(v);   // row_half_mirror
-  v += dpp_f64<0x140>(v);   // row_mirror
-  return v;
-}
 
 #define RE_G 16                      // lanes per row (one DPP row)
 #define RE_RPI (64 / RE_G)           // rows per wave instruction
@@ -597,7 +496,6 @@ __global__ __launch_bounds__(RE_THREADS) void re_tron_csr_kernel(ReTronArgs a) {
   int it = 0, fails = 0, reason = 0;
   bool active = true;
   if (delta == 0.0) { reason = 4; active = false; }
-  const double eta0 = 1e-4, eta1 = 0.25, eta2 = 0.75, sg1 = 0.25, sg2 = 0.5, sg3 = 4.0;
   const int guard_max = a.max_iter * (a.max_fail + 1) + 5;
   for (int guard = 0; active && guard < guard_max; ++guard) {
     // ---- truncated CG at W (Hessian weights D[cur]). Per CG step: the Hessian-vector pass, ONE sweep that
@@ -648,32 +546,17 @@ __global__ __launch_bounds__(RE_THREADS) void re_tron_csr_kernel(ReTronArgs a) {
       if constexpr (SHIFT) {
         if (own0) acc[i0] = hi0;
       }
-      const double dhd = s5[0], std_ = s5[1], dtd = s5[2], rh = s5[3], hh = s5[4];
-      const double alpha = rtr / (dhd == 0.0 ? 1.0 : dhd);
-      double tn = sts + 2.0 * alpha * std_ + alpha * alpha * dtd;
-      tn = tn > 0.0 ? tn : 0.0;
-      const double dsq = delta * delta;
-      const bool hit = tn > dsq;
-      double al = alpha;
-      if (hit) {
-        const double q = std_ * std_ + dtd * (dsq - sts);
-        const double rad = sqrt(q > 0.0 ? q : 0.0);
-        const double den1 = std_ + rad;
-        al = std_ >= 0.0 ? (dsq - sts) / (den1 > 1e-300 ? den1 : 1e-300) : (rad - std_) / (dtd > 1e-300 ? dtd : 1e-300);
-      }
-      double rn = rtr - 2.0 * al * rh + al * al * hh;
-      rn = rn > 0.0 ? rn : 0.0;
-      const double beta = rn / (rtr == 0.0 ? 1.0 : rtr);
+      const TronCgStep c = tron_cg_step(rtr, sts, delta, s5[0], s5[1], s5[2], s5[3], s5[4]);
       for (int j = tid; j < d; j += RE_THREADS) {
         const double dj = sD[j];
-        sS[j] += al * dj;
-        const double r = sR[j] - al * acc[j];
+        sS[j] += c.al * dj;
+        const double r = sR[j] - c.al * acc[j];
         sR[j] = r;
-        if (!hit) sD[j] = r + beta * dj;
+        if (!c.hit) sD[j] = r + c.beta * dj;
       }
-      if (hit) break;
-      rtr = rn;
-      sts = tn;
+      if (c.hit) break;
+      rtr = c.rn;
+      sts = c.tn;
     }
     // ---- trial point W + step (in the direction slot), trust-region update, acceptance
     double s3[3] = {0.0, 0.0, 0.0};
@@ -688,17 +571,8 @@ __global__ __launch_bounds__(RE_THREADS) void re_tron_csr_kernel(ReTronArgs a) {
     const double gs = s3[0], pred = -0.5 * (gs - s3[1]), snorm = sqrt(s3[2]);
     double gn2;
     const double fn = value_grad(sD, cur ^ 1, false, gn2);   // trial gradient in acc[0 .. d)
-    const double actual = f - fn;
-    if (it == 0) delta = fmin(delta, snorm);
-    const double den = fn - f - gs;
-    const double alr = den <= 0.0 ? sg3 : fmax(sg1, -0.5 * gs / (den == 0.0 ? 1.0 : den));
-    double nd;
-    if (actual < eta0 * pred) nd = fmin(fmax(alr, sg1) * snorm, sg2 * delta);
-    else if (actual < eta1 * pred) nd = fmax(sg1 * delta, fmin(alr * snorm, sg2 * delta));
-    else if (actual < eta2 * pred) nd = fmax(sg1 * delta, fmin(alr * snorm, sg3 * delta));
-    else nd = fmax(delta, fmin(alr * snorm, sg3 * delta));
-    delta = nd;
-    const bool accept = actual > eta0 * pred;
+    delta = tron_radius(delta, snorm, gs, f, fn, pred, it == 0);
+    const bool accept = tron_accept(f, fn, pred);
     const double f_prev = f;
     if (accept) {
       for (int j = tid; j < d; j += RE_THREADS) {
@@ -714,11 +588,7 @@ __global__ __launch_bounds__(RE_THREADS) void re_tron_csr_kernel(ReTronArgs a) {
       ++fails;
     }
     const bool not_impr = !accept && fails >= a.max_fail;
-    int rc = 0;
-    if (accept && sqrt(gnorm2) <= grad_tol) rc = 4;
-    if (accept && fabs(f - f_prev) <= loss_tol) rc = 3;
-    if (not_impr) rc = 2;
-    if ((accept || not_impr) && it >= a.max_iter) rc = 1;
+    const int rc = tron_reason(accept, not_impr, gnorm2, grad_tol, f, f_prev, loss_tol, it, a.max_iter);
     if (rc > 0) { reason = rc; active = false; }
   }
   __syncthreads();
@@ -1122,7 +992,6 @@ void re_tron_lean_kernel(ReTronArgs a) {
   int it = 0, fails = 0, reason = 0;
   bool active = true;
   if (delta == 0.0) { reason = 4; active = false; }
-  const double eta0 = 1e-4, eta1 = 0.25, eta2 = 0.75, sg1 = 0.25, sg2 = 0.5, sg3 = 4.0;
   const int guard_max = a.max_iter * (a.max_fail + 1) + 5;
   for (int guard = 0; active && guard < guard_max; ++guard) {
     // truncated CG at W: one Hessian-vector pass, one combine sweep with the five dot products, one update sweep
@@ -1162,36 +1031,21 @@ void re_tron_lean_kernel(ReTronArgs a) {
         }
       }
       block_sums<5, LEAN_NW>(s5, red, parity);
-      const double dhd = s5[0], std_ = s5[1], dtd = s5[2], rh = s5[3], hh = s5[4];
-      const double alpha = rtr / (dhd == 0.0 ? 1.0 : dhd);
-      double tn = sts + 2.0 * alpha * std_ + alpha * alpha * dtd;
-      tn = tn > 0.0 ? tn : 0.0;
-      const double dsq = delta * delta;
-      const bool hit = tn > dsq;
-      double al = alpha;
-      if (hit) {
-        const double qq = std_ * std_ + dtd * (dsq - sts);
-        const double rad = sqrt(qq > 0.0 ? qq : 0.0);
-        const double den1 = std_ + rad;
-        al = std_ >= 0.0 ? (dsq - sts) / (den1 > 1e-300 ? den1 : 1e-300) : (rad - std_) / (dtd > 1e-300 ? dtd : 1e-300);
-      }
-      double rn = rtr - 2.0 * al * rh + al * al * hh;
-      rn = rn > 0.0 ? rn : 0.0;
-      const double beta = rn / (rtr == 0.0 ? 1.0 : rtr);
+      const TronCgStep c = tron_cg_step(rtr, sts, delta, s5[0], s5[1], s5[2], s5[3], s5[4]);
 #pragma unroll
       for (int q = 0; q < J; ++q) {
         const int j = tid + LEAN_THREADS * q;
         if (j < d) {
           const double dj = sD[j];
-          S[q] += al * dj;
-          const double r = R[q] - al * H[q];
+          S[q] += c.al * dj;
+          const double r = R[q] - c.al * H[q];
           R[q] = r;
-          if (!hit) sD[j] = r + beta * dj;
+          if (!c.hit) sD[j] = r + c.beta * dj;
         }
       }
-      if (hit) break;
-      rtr = uniform_f64(rn);
-      sts = uniform_f64(tn);
+      if (c.hit) break;
+      rtr = uniform_f64(c.rn);
+      sts = uniform_f64(c.tn);
     }
     // trial point W + step (in sD), trust-region update, acceptance
     double s3[3] = {0.0, 0.0, 0.0};
@@ -1210,17 +1064,8 @@ void re_tron_lean_kernel(ReTronArgs a) {
     const double gs = s3[0], pred = -0.5 * (gs - s3[1]), snorm = sqrt(s3[2]);
     double gn2;
     const double fn = value_grad(false, cur ^ 1, gn2);   // trial gradient in acc[0 .. d)
-    const double actual = f - fn;
-    if (it == 0) delta = uniform_f64(fmin(delta, snorm));
-    const double den = fn - f - gs;
-    const double alr = den <= 0.0 ? sg3 : fmax(sg1, -0.5 * gs / (den == 0.0 ? 1.0 : den));
-    double nd;
-    if (actual < eta0 * pred) nd = fmin(fmax(alr, sg1) * snorm, sg2 * delta);
-    else if (actual < eta1 * pred) nd = fmax(sg1 * delta, fmin(alr * snorm, sg2 * delta));
-    else if (actual < eta2 * pred) nd = fmax(sg1 * delta, fmin(alr * snorm, sg3 * delta));
-    else nd = fmax(delta, fmin(alr * snorm, sg3 * delta));
-    delta = uniform_f64(nd);
-    const bool accept = actual > eta0 * pred;
+    delta = uniform_f64(tron_radius(delta, snorm, gs, f, fn, pred, it == 0));
+    const bool accept = tron_accept(f, fn, pred);
     const double f_prev = f;
     if (accept) {
 #pragma unroll
@@ -1247,11 +1092,7 @@ void re_tron_lean_kernel(ReTronArgs a) {
       grad_tol = sqrt(g0) * a.tol;
       g0_lazy = false;
     }
-    int rc = 0;
-    if (accept && sqrt(gnorm2) <= grad_tol) rc = 4;
-    if (accept && fabs(f - f_prev) <= loss_tol) rc = 3;
-    if (not_impr) rc = 2;
-    if ((accept || not_impr) && it >= a.max_iter) rc = 1;
+    const int rc = tron_reason(accept, not_impr, gnorm2, grad_tol, f, f_prev, loss_tol, it, a.max_iter);
     if (rc > 0) { reason = rc; active = false; }
   }
   __syncthreads();
@@ -1267,97 +1108,57 @@ void re_tron_lean_kernel(ReTronArgs a) {
 
 // ============================================================================================================
 // Tall-narrow entities (d_e <= 64 coefficients, typically more rows than coefficients): ONE WAVE PER ENTITY, the
-// whole TRON with the EXACT per-entity Hessian H_e = X_e^T D X_e + l2 I. No workgroup barriers: the waves of a
-// workgroup are independent entities, every reduction is a DPP / readlane wave sum, LDS hand-offs between the
-// lanes of one wave are ordered by wave_sync (in-order LDS per wave + a compiler fence).
-// * Coefficient-space vectors live in registers: lane j holds w_j, g_j, step_j, r_j, dir_j (j < d_e <= 64).
-// * Row passes stage RT_RB = 16 rows at a time as a dense [16][DP + 4] LDS block (row stride DP + 4: the
-//   quad-per-row margin reads are bank-conflict free): the entries are scattered from registers and zeroed again
-//   after use, and the NEXT block's entries (and the row pointers two blocks ahead) are already in flight while a
-//   block computes, so a pass costs about one global-memory latency, not one per block.
-// * Margins: a lane quad per row; gradient: lane j sums X[r][j] t_r over the 16 rows in a fixed order (no
-//   atomics: deterministic by construction).
-// * Hessian: per 4 staged rows one v_mfma_f64_16x16x4f64 per upper-triangle 16 x 16 tile (all tiles in the one
-//   wave, fixed k order), written to LDS EXACTLY symmetric (diagonal tiles mirrored from their upper half), so a
-//   CG step reads column j of H (consecutive lanes: conflict-free) for (H d)_j. For d_e <= 32 (FH) the Hessian
-//   at the trial point is formed INSIDE the trial point's function evaluation into a second LDS buffer (adopted
-//   when the step is accepted): one row pass per TRON iteration. Wider entities run a separate Hessian pass.
+// whole TRON with the EXACT per-entity Hessian in LDS -- tron_dense_wave (tron_core.h), which mf_tron_kernel runs
+// too. This file supplies the row source: the entity's CSR rows, 16 at a time, their entries scattered from
+// registers into the dense LDS block (zero at the start) and zeroed again after use; the NEXT block's entries (and
+// the row pointers two blocks ahead) are already in flight while a block computes. For d_e <= 32 (FH) the Hessian
+// at the trial point is formed inside the trial point's function evaluation; wider entities keep the Hessian
+// weights D per row and run a separate Hessian pass.
 // ============================================================================================================
-typedef double v4d __attribute__((ext_vector_type(4)));
-#define RT_RB 16
-
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// Sum over the 4 lanes of a quad, in every lane of the quad (fixed order).
-__device__ __forceinline__ double quad_total(double v) {
-  v += dpp_f64<0xB1>(v);    // quad_perm [1,0,3,2]
-  v += dpp_f64<0x4E>(v);    // quad_perm [2,3,0,1]
-  return v;
-}
-
 template <int T>
-struct TallCfg {
-  static constexpr int DP = 16 * T;                  // padded coefficient count
-  static constexpr int XS = DP + 4;                  // staged row stride (doubles)
-  static constexpr bool FH = T <= 2;                 // Hessian fused into the function evaluation (2 H buffers)
-  static constexpr int WORDS = (FH ? 2 : 1) * DP * DP + RT_RB * XS + DP + 2 * RT_RB;   // LDS doubles per wave
-};
-
-template <int T, int LOSS>
-__global__ __launch_bounds__(64) void re_tron_tall_kernel(ReTronArgs a) {
-  using C = TallCfg<T>;
-  constexpr int DP = C::DP, XS = C::XS, NT = T * (T + 1) / 2, KE = T;
-  constexpr bool FH = C::FH;
-  extern __shared__ __attribute__((aligned(16))) double smem[];
-  const int lane = threadIdx.x;
-  const int e = a.order[blockIdx.x];
-  double* const H0 = smem;                              // [DP][DP] Hessian buffers, exactly symmetric
-  double* const H1 = smem + (FH ? DP * DP : 0);
-  double* Xs = smem + (FH ? 2 : 1) * DP * DP;           // [RT_RB][XS] staged rows (zero between blocks)
-  double* sV = Xs + RT_RB * XS;                         // [DP] vector broadcast to the lanes (margins / CG)
-  double* sT = sV + DP;                                 // [RT_RB] per staged row: gradient weight t_r
-  double* sD = sT + RT_RB;                              // [RT_RB] per staged row: Hessian weight D_r
-  int hc = 0;                                           // (hc ? H1 : H0) = Hessian at the current point
-  const long long r0 = a.row_ptr[e], r1 = a.row_ptr[e + 1];
-  const long long c0 = a.col_ptr[e];
-  const int d = (int)(a.col_ptr[e + 1] - c0);
-  const bool own = lane < d;                            // lane j owns coefficient j
-  double* D[2] = {a.scr, a.scr + a.n_rows};
-  double* Z[2] = {a.scr + 2 * a.n_rows, a.scr + 3 * a.n_rows};
-  int cur = 0, npass = 0;
-  double* Wg = a.W + c0;
-  const int grp = lane >> 4, gl = lane & 15;
-  // entity-local 32-bit offsets from per-entity bases (one VGPR per address)
-  const long long e0 = a.nip[r0];
-  const uint16_t* __restrict__ lcol = a.lcol + e0;
-  const double* __restrict__ val = a.val + e0;
-  const int nrows = (int)(r1 - r0);
-  for (int i = lane; i < RT_RB * XS; i += 64) Xs[i] = 0.0;
-
+struct TallRows {
+  static constexpr bool FH = T <= 2;
+  static constexpr int XS = TronDenseCfg<T, FH>::XS, KE = T;     // KE entries per lane and row: rows of <= 16 T
   struct Blk {
-    int c[RT_RB / 4][KE];
-    double v[RT_RB / 4][KE];
+    int c[TRON_RB / 4][KE];
+    double v[TRON_RB / 4][KE];
     double rs[3];
   };
-  // row pointers of block b (lane q <= RT_RB: entity-local offset of row b + q)
-  auto fetch_np = [&](int b) -> int {
-    const int ip = b + (lane <= RT_RB ? lane : RT_RB);
+  const ReTronArgs& a;
+  const int lane = threadIdx.x, grp = lane >> 4, gl = lane & 15;
+  const long long r0;
+  const int nrows, nc;
+  double* const Wg;
+  double* const D0;
+  double* const D1;
+  double* const Z0;
+  double* const Z1;
+  // entity-local 32-bit offsets from per-entity bases (one VGPR per address)
+  const long long e0;
+  const uint16_t* const lcol;
+  const double* const val;
+
+  __device__ __forceinline__ TallRows(const ReTronArgs& a_, int e)
+      : a(a_), r0(a_.row_ptr[e]), nrows((int)(a_.row_ptr[e + 1] - r0)),
+        nc((int)(a_.col_ptr[e + 1] - a_.col_ptr[e])), Wg(a_.W + a_.col_ptr[e]), D0(a_.scr), D1(a_.scr + a_.n_rows),
+        Z0(a_.scr + 2 * a_.n_rows), Z1(a_.scr + 3 * a_.n_rows), e0(a_.nip[r0]), lcol(a_.lcol + e0),
+        val(a_.val + e0) {}
+
+  // row pointers of block b (lane q <= TRON_RB: entity-local offset of row b + q)
+  __device__ __forceinline__ int fetch(int b) const {
+    const int ip = b + (lane <= TRON_RB ? lane : TRON_RB);
     return b < nrows ? (int)(a.nip[r0 + (ip < nrows ? ip : nrows)] - e0) : 0;
-  };
+  }
   // issue the loads of block b (entries + per-row scalars: mode 0 = D[cur] in rs[0], else wt / off / y)
-  auto issue = [&](Blk& B, int b, int np, int mode) {
+  __device__ __forceinline__ void issue(Blk& B, int b, int np, int mode, int cur) const {
     B.rs[0] = B.rs[1] = B.rs[2] = 0.0;
-    if (lane < RT_RB && b + lane < nrows) {
+    if (lane < TRON_RB && b + lane < nrows) {
       const long long i = r0 + b + lane;
-      if (mode == 0) B.rs[0] = D[cur][i];
+      if (mode == 0) B.rs[0] = (cur ? D1 : D0)[i];
       else { B.rs[0] = a.wt[i]; B.rs[1] = a.off[i]; B.rs[2] = a.y[i]; }
     }
 #pragma unroll
-    for (int u = 0; u < RT_RB / 4; ++u) {
+    for (int u = 0; u < TRON_RB / 4; ++u) {
       const int q = u * 4 + grp;
       const int lo = __shfl(np, q, 64), hi = __shfl(np, q + 1, 64);
 #pragma unroll
@@ -1368,246 +1169,26 @@ __global__ __launch_bounds__(64) void re_tron_tall_kernel(ReTronArgs a) {
         B.v[u][k] = in ? val[p] : 0.0;
       }
     }
-  };
-  auto scatter = [&](const Blk& B, bool zero) {
+  }
+  template <bool ZERO>
+  __device__ __forceinline__ void scatter(const Blk& B, double* Xs) const {
 #pragma unroll
-    for (int u = 0; u < RT_RB / 4; ++u)
+    for (int u = 0; u < TRON_RB / 4; ++u)
 #pragma unroll
       for (int k = 0; k < KE; ++k)
-        if (B.c[u][k] >= 0) Xs[(u * 4 + grp) * XS + B.c[u][k]] = zero ? 0.0 : B.v[u][k];
-  };
-  // Pipelined pass over the entity's blocks: body(b, B) runs with block b staged in Xs (and its loads in B.rs).
-  auto pass = [&](int mode, auto&& body) {
-    Blk A, B2;
-    int np = fetch_np(0);
-    issue(A, 0, np, mode);
-    np = fetch_np(RT_RB);
-    for (int b = 0; b < nrows; b += 2 * RT_RB) {
-      const bool hasB = b + RT_RB < nrows;
-      if (hasB) issue(B2, b + RT_RB, np, mode);
-      np = fetch_np(b + 2 * RT_RB);
-      scatter(A, false);
-      wave_sync();
-      body(b, A);
-      wave_sync();
-      scatter(A, true);
-      if (!hasB) break;
-      const bool hasA = b + 2 * RT_RB < nrows;
-      if (hasA) issue(A, b + 2 * RT_RB, np, mode);
-      np = fetch_np(b + 3 * RT_RB);
-      scatter(B2, false);
-      wave_sync();
-      body(b + RT_RB, B2);
-      wave_sync();
-      scatter(B2, true);
-      if (!hasA) break;
-    }
-  };
-  // MFMA accumulation of X_blk^T diag(w) X_blk for the staged block (w in LDS ``sw``)
-  auto hess_block = [&](v4d (&cacc)[NT], const double* sw) {
-    const int rr = lane & 15, kk = lane >> 4;
-#pragma unroll 1
-    for (int kg = 0; kg < RT_RB / 4; ++kg) {
-      const int k = kg * 4 + kk;
-      const double dk = sw[k];
-      const double* xk = Xs + k * XS;
-      int t = 0;
-#pragma unroll
-      for (int ti = 0; ti < T; ++ti)
-#pragma unroll
-        for (int tj = ti; tj < T; ++tj, ++t)
-          cacc[t] = __builtin_amdgcn_mfma_f64_16x16x4f64(xk[ti * 16 + rr], dk * xk[tj * 16 + rr], cacc[t], 0, 0, 0);
-    }
-  };
-  auto store_hess = [&](v4d (&cacc)[NT], double* H) {
-    int t = 0;
-#pragma unroll
-    for (int ti = 0; ti < T; ++ti)
-#pragma unroll
-      for (int tj = ti; tj < T; ++tj, ++t)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          // accumulator i of lane l holds C[(l >> 4) + 4 i][l & 15] of the tile
-          const int lr = (lane >> 4) + 4 * i, lc = lane & 15;
-          const int row = ti * 16 + lr, col = tj * 16 + lc;
-          if (ti != tj || lr <= lc) {
-            H[row * DP + col] = cacc[t][i];
-            H[col * DP + row] = cacc[t][i];
-          }
-        }
-    wave_sync();
-    if (lane < DP) H[lane * DP + lane] += a.l2;
-    wave_sync();
-  };
+        if (B.c[u][k] >= 0) Xs[(u * 4 + grp) * XS + B.c[u][k]] = ZERO ? 0.0 : B.v[u][k];
+  }
+  __device__ __forceinline__ void stage(const Blk& B, double* Xs) const { scatter<false>(B, Xs); }
+  __device__ __forceinline__ void unstage(const Blk& B, double* Xs) const { scatter<true>(B, Xs); }
+};
 
-  // value + gradient at the lane-held vector ``vj`` (written to sV here). mode 1: writes Z buffer ``nb`` (and D
-  // when the Hessian has its own pass); mode 2 (the state at zero): no scratch writes. ``Hout`` (FH only): the
-  // Hessian at vj is formed in the same pass. Returns f; gj = this lane's gradient component (l2 included).
-  auto value_grad = [&](double vj, int mode, int nb, double& gj, double* Hout) -> double {
-    ++npass;
-    if (lane < DP) sV[lane] = own ? vj : 0.0;
-    const int r = lane >> 2, q = lane & 3;
-    double fp = 0.0, g = 0.0;
-    v4d cacc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) cacc[t] = v4d{0.0, 0.0, 0.0, 0.0};
-    pass(1, [&](int b, const Blk& B) {
-      double s = 0.0;
-#pragma unroll 4
-      for (int cc = 0; cc < DP / 4; ++cc) s = fma(Xs[r * XS + q + 4 * cc], sV[q + 4 * cc], s);
-      s = quad_total(s);
-      const double wt = __shfl(B.rs[0], r, 64), of = __shfl(B.rs[1], r, 64), yy = __shfl(B.rs[2], r, 64);
-      double t = 0.0, h = 0.0;
-      if (b + r < nrows) {
-        const long long i = r0 + b + r;
-        double l, dl, d2;
-        loss_t<LOSS>(s + of, yy, l, dl, d2);
-        t = wx(wt, dl);
-        h = wx(wt, d2);
-        if (q == 0) {
-          fp += wx(wt, l);
-          if (mode == 1) {
-            Z[nb][i] = s;
-            if (!FH) D[nb][i] = h;
-          }
-        }
-      }
-      if (q == 0) { sT[r] = t; sD[r] = h; }
-      wave_sync();
-      if (lane < DP) {
-#pragma unroll 4
-        for (int rr = 0; rr < RT_RB; ++rr) g = fma(Xs[rr * XS + lane], sT[rr], g);
-      }
-      if (FH && Hout != nullptr) hess_block(cacc, sD);
-    });
-    if (FH && Hout != nullptr) store_hess(cacc, Hout);
-    gj = own ? g + a.l2 * vj : 0.0;
-    return wave_total(fp) + 0.5 * a.l2 * wave_total(own ? vj * vj : 0.0);
-  };
-  // separate Hessian pass at the current point (entities wider than 32): H = X^T diag(D[cur]) X + l2 I
-  auto form_hessian = [&]() {
-    ++npass;
-    v4d cacc[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) cacc[t] = v4d{0.0, 0.0, 0.0, 0.0};
-    pass(0, [&](int b, const Blk& B) {
-      if (lane < RT_RB) sD[lane] = B.rs[0];
-      wave_sync();
-      hess_block(cacc, sD);
-    });
-    store_hess(cacc, (hc ? H1 : H0));
-  };
-
-  double Wj = own ? Wg[lane] : 0.0, Gj;
-  double f = value_grad(Wj, 1, cur, Gj, FH ? (hc ? H1 : H0) : nullptr);
-  double gnorm2 = wave_total(Gj * Gj);
-  const double nz = wave_total(own && Wj != 0.0 ? 1.0 : 0.0);
-  double f0z = f, g0n = sqrt(gnorm2);
-  if (nz != 0.0) {
-    double g0j;
-    f0z = value_grad(0.0, 2, 0, g0j, nullptr);
-    g0n = sqrt(wave_total(g0j * g0j));
-  }
-  const double loss_tol = f0z * a.tol, grad_tol = g0n * a.tol;
-  double delta = sqrt(gnorm2);
-  int it = 0, fails = 0, reason = 0;
-  bool active = true, need_h = !FH;
-  if (delta == 0.0) { reason = 4; active = false; }
-  const double eta0 = 1e-4, eta1 = 0.25, eta2 = 0.75, sg1 = 0.25, sg2 = 0.5, sg3 = 4.0;
-  const int guard_max = a.max_iter * (a.max_fail + 1) + 5;
-  for (int guard = 0; active && guard < guard_max; ++guard) {
-    if (need_h) { form_hessian(); need_h = false; }
-    const double* H = (hc ? H1 : H0);
-    // ---- truncated CG on the LDS Hessian: per step one column-read mat-vec and five wave sums
-    double Sj = 0.0, Rj = -Gj, Dj = -Gj;
-    double rtr = gnorm2, sts = 0.0;
-    const double cg_tol2 = 0.01 * gnorm2;
-    for (int k = 0; k < a.max_cg; ++k) {
-      if (!(rtr > cg_tol2)) break;
-      if (lane < DP) sV[lane] = Dj;
-      wave_sync();
-      double h0 = 0.0, h1 = 0.0;
-      if (lane < DP) {
-#pragma unroll 2
-        for (int cc = 0; cc < DP; cc += 2) {
-          h0 = fma(H[cc * DP + lane], sV[cc], h0);
-          h1 = fma(H[(cc + 1) * DP + lane], sV[cc + 1], h1);
-        }
-      }
-      wave_sync();
-      const double hj = own ? h0 + h1 : 0.0;
-      const double dhd = wave_total(Dj * hj), std_ = wave_total(Sj * Dj), dtd = wave_total(Dj * Dj);
-      const double rh = wave_total(Rj * hj), hh = wave_total(hj * hj);
-      const double alpha = rtr / (dhd == 0.0 ? 1.0 : dhd);
-      double tn = sts + 2.0 * alpha * std_ + alpha * alpha * dtd;
-      tn = tn > 0.0 ? tn : 0.0;
-      const double dsq = delta * delta;
-      const bool hit = tn > dsq;
-      double al = alpha;
-      if (hit) {
-        const double qq = std_ * std_ + dtd * (dsq - sts);
-        const double rad = sqrt(qq > 0.0 ? qq : 0.0);
-        const double den1 = std_ + rad;
-        al = std_ >= 0.0 ? (dsq - sts) / (den1 > 1e-300 ? den1 : 1e-300) : (rad - std_) / (dtd > 1e-300 ? dtd : 1e-300);
-      }
-      double rn = rtr - 2.0 * al * rh + al * al * hh;
-      rn = rn > 0.0 ? rn : 0.0;
-      const double beta = rn / (rtr == 0.0 ? 1.0 : rtr);
-      Sj += al * Dj;
-      Rj -= al * hj;
-      if (hit) break;
-      Dj = Rj + beta * Dj;
-      rtr = rn;
-      sts = tn;
-    }
-    // ---- trial point (its Hessian formed in the same pass when FH), trust-region update, acceptance
-    const double gs = wave_total(Gj * Sj), pred = -0.5 * (gs - wave_total(Sj * Rj)), snorm = sqrt(wave_total(Sj * Sj));
-    const double Tj = own ? Wj + Sj : 0.0;
-    double Gn;
-    const double fn = value_grad(Tj, 1, cur ^ 1, Gn, FH ? (hc ? H0 : H1) : nullptr);
-    const double gn2 = wave_total(Gn * Gn);
-    const double actual = f - fn;
-    if (it == 0) delta = fmin(delta, snorm);
-    const double den = fn - f - gs;
-    const double alr = den <= 0.0 ? sg3 : fmax(sg1, -0.5 * gs / (den == 0.0 ? 1.0 : den));
-    double nd;
-    if (actual < eta0 * pred) nd = fmin(fmax(alr, sg1) * snorm, sg2 * delta);
-    else if (actual < eta1 * pred) nd = fmax(sg1 * delta, fmin(alr * snorm, sg2 * delta));
-    else if (actual < eta2 * pred) nd = fmax(sg1 * delta, fmin(alr * snorm, sg3 * delta));
-    else nd = fmax(delta, fmin(alr * snorm, sg3 * delta));
-    delta = nd;
-    const bool accept = actual > eta0 * pred;
-    const double f_prev = f;
-    if (accept) {
-      Wj = Tj;
-      Gj = Gn;
-      gnorm2 = gn2;
-      f = fn;
-      cur ^= 1;
-      ++it;
-      fails = 0;
-      if (FH) hc ^= 1;
-      else need_h = true;
-    } else {
-      ++fails;
-    }
-    const bool not_impr = !accept && fails >= a.max_fail;
-    int rc = 0;
-    if (accept && sqrt(gnorm2) <= grad_tol) rc = 4;
-    if (accept && fabs(f - f_prev) <= loss_tol) rc = 3;
-    if (not_impr) rc = 2;
-    if ((accept || not_impr) && it >= a.max_iter) rc = 1;
-    if (rc > 0) { reason = rc; active = false; }
-  }
-  if (own) Wg[lane] = Wj;
-  if (a.zout != nullptr) {
-    const double* zc = Z[cur];
-    for (long long i = r0 + lane; i < r1; i += 64) a.zout[i] = zc[i];
-  }
-  if (lane == 0) {
-    a.f[e] = f; a.iters[e] = it; a.reason[e] = reason;
-    if (a.npass != nullptr) a.npass[e] = npass;
-  }
+template <int T, int LOSS>
+__global__ __launch_bounds__(64) void re_tron_tall_kernel(ReTronArgs a) {
+  using C = TronDenseCfg<T, TallRows<T>::FH>;
+  extern __shared__ __attribute__((aligned(16))) double smem[];
+  const int e = a.order[blockIdx.x];
+  for (int i = threadIdx.x; i < TRON_RB * C::XS; i += 64) smem[C::XOFF + i] = 0.0;    // the staged block starts empty
+  tron_dense_wave<T, LOSS>(a, e, TallRows<T>(a, e), smem);
 }
 
 // ============================================================================================================
@@ -1719,7 +1300,6 @@ __global__ __launch_bounds__(64) void rs_tron_big_kernel(int B, int n, const dou
 #pragma unroll
     for (int e = 0; e < E; ++e) gr[e] = on[e] ? gr[e] + l2 * v[e] : 0.0;
   };
-  const double eta0 = 1e-4, eta1 = 0.25, eta2 = 0.75, s1 = 0.25, s2 = 0.5, s3 = 4.0;
   double f, gr[E], Dw[E], Z[E];
   vg(W, f, gr, Dw, Z);
   double f0z, g0n;
@@ -1797,18 +1377,9 @@ __global__ __launch_bounds__(64) void rs_tron_big_kernel(int B, int n, const dou
     const double pred = -0.5 * (gs - gsum2(step, r));
     double fn, gn[E], Dn[E], Zn[E];
     vg(Wn, fn, gn, Dn, Zn);
-    const double actual = f - fn;
     const double snorm = sqrt(gsum2(step, step));
-    if (it == 0) delta = fmin(delta, snorm);
-    const double den = fn - f - gs;
-    const double al = den <= 0.0 ? s3 : fmax(s1, -0.5 * gs / (den == 0.0 ? 1.0 : den));
-    double nd;
-    if (actual < eta0 * pred) nd = fmin(fmax(al, s1) * snorm, s2 * delta);
-    else if (actual < eta1 * pred) nd = fmax(s1 * delta, fmin(al * snorm, s2 * delta));
-    else if (actual < eta2 * pred) nd = fmax(s1 * delta, fmin(al * snorm, s3 * delta));
-    else nd = fmax(delta, fmin(al * snorm, s3 * delta));
-    delta = nd;
-    const bool accept = actual > eta0 * pred;
+    delta = tron_radius(delta, snorm, gs, f, fn, pred, it == 0);
+    const bool accept = tron_accept(f, fn, pred);
     const double f_prev = f;
     if (accept) {
 #pragma unroll
@@ -1820,12 +1391,7 @@ __global__ __launch_bounds__(64) void rs_tron_big_kernel(int B, int n, const dou
       ++fails;
     }
     const bool not_impr = !accept && fails >= max_fail;
-    const double gnorm = sqrt(gsum2(gr, gr));
-    int rc = 0;
-    if (accept && gnorm <= grad_tol) rc = 4;
-    if (accept && fabs(f - f_prev) <= loss_tol) rc = 3;
-    if (not_impr) rc = 2;
-    if ((accept || not_impr) && it >= max_iter) rc = 1;
+    const int rc = tron_reason(accept, not_impr, gsum2(gr, gr), grad_tol, f, f_prev, loss_tol, it, max_iter);
     if (rc > 0) { reason = rc; active = false; }
   }
 #pragma unroll
@@ -2137,7 +1703,6 @@ __global__ __launch_bounds__(RS_THREADS) void re_tron_res_kernel(ReTronArgs a, R
       T[DELTA] = sqrt(T[GN2]);
       TI[0] = 0; TI[1] = 0; TI[2] = T[DELTA] == 0.0 ? 4 : 0; TI[3] = T[DELTA] == 0.0 ? 0 : 1;
     }
-    const double eta0 = 1e-4, eta1 = 0.25, eta2 = 0.75, sg1 = 0.25, sg2 = 0.5, sg3 = 4.0;
     const int guard_max = a.max_iter * (a.max_fail + 1) + 5;
     for (int guard = 0; TI[3] && guard < guard_max; ++guard) {
       for (int jj = tid; jj < d; jj += RS_THREADS) {
@@ -2169,32 +1734,17 @@ __global__ __launch_bounds__(RS_THREADS) void re_tron_res_kernel(ReTronArgs a, R
           s5[4] += h * h;
         }
         block_sums8<5>(s5, red, parity);
-        const double dhd = s5[0], std_ = s5[1], dtd = s5[2], rh = s5[3], hh = s5[4];
-        const double alpha = rtr / (dhd == 0.0 ? 1.0 : dhd);
-        double tn = sts + 2.0 * alpha * std_ + alpha * alpha * dtd;
-        tn = tn > 0.0 ? tn : 0.0;
-        const double dsq = delta * delta;
-        const bool hit = tn > dsq;
-        double al = alpha;
-        if (hit) {
-          const double qq = std_ * std_ + dtd * (dsq - sts);
-          const double rad = sqrt(qq > 0.0 ? qq : 0.0);
-          const double den1 = std_ + rad;
-          al = std_ >= 0.0 ? (dsq - sts) / (den1 > 1e-300 ? den1 : 1e-300) : (rad - std_) / (dtd > 1e-300 ? dtd : 1e-300);
-        }
-        double rn = rtr - 2.0 * al * rh + al * al * hh;
-        rn = rn > 0.0 ? rn : 0.0;
-        const double beta = rn / (rtr == 0.0 ? 1.0 : rtr);
+        const TronCgStep c = tron_cg_step(rtr, sts, delta, s5[0], s5[1], s5[2], s5[3], s5[4]);
         for (int jj = tid; jj < d; jj += RS_THREADS) {
           const double dj = sV[jj];
-          sS[jj] += al * dj;
-          const double r = sR[jj] - al * sH[jj];
+          sS[jj] += c.al * dj;
+          const double r = sR[jj] - c.al * sH[jj];
           sR[jj] = r;
-          if (!hit) sV[jj] = r + beta * dj;
+          if (!c.hit) sV[jj] = r + c.beta * dj;
         }
-        if (hit) break;
-        T[RTR] = rn;
-        T[STS] = tn;
+        if (c.hit) break;
+        T[RTR] = c.rn;
+        T[STS] = c.tn;
       }
       // ---- trial point W + step (into sV), trust-region update, acceptance
       __syncthreads();
@@ -2209,22 +1759,12 @@ __global__ __launch_bounds__(RS_THREADS) void re_tron_res_kernel(ReTronArgs a, R
       block_sums8<3>(s3, red, parity);
       const double gs = s3[0], pred = -0.5 * (gs - s3[1]), snorm = sqrt(s3[2]);
       // state read BEFORE the trial evaluation's barriers (a faster thread rewrites it after them)
-      const double f = T[F], gn2_old = T[GN2];
-      double delta = T[DELTA];
+      const double f = T[F], gn2_old = T[GN2], delta = T[DELTA];
       int it = TI[0], fails = TI[1];
       double gn2;
       const double fn = value_grad(sV, 1, cur ^ 1, gn2);     // trial gradient in sH
-      const double actual = f - fn;
-      if (it == 0) delta = fmin(delta, snorm);
-      const double den = fn - f - gs;
-      const double alr = den <= 0.0 ? sg3 : fmax(sg1, -0.5 * gs / (den == 0.0 ? 1.0 : den));
-      double nd;
-      if (actual < eta0 * pred) nd = fmin(fmax(alr, sg1) * snorm, sg2 * delta);
-      else if (actual < eta1 * pred) nd = fmax(sg1 * delta, fmin(alr * snorm, sg2 * delta));
-      else if (actual < eta2 * pred) nd = fmax(sg1 * delta, fmin(alr * snorm, sg3 * delta));
-      else nd = fmax(delta, fmin(alr * snorm, sg3 * delta));
-      T[DELTA] = nd;
-      const bool accept = actual > eta0 * pred;
+      T[DELTA] = tron_radius(delta, snorm, gs, f, fn, pred, it == 0);
+      const bool accept = tron_accept(f, fn, pred);
       double fc = f, gnc = gn2_old;
       if (accept) {
         for (int jj = tid; jj < d; jj += RS_THREADS) {
@@ -2242,11 +1782,7 @@ __global__ __launch_bounds__(RS_THREADS) void re_tron_res_kernel(ReTronArgs a, R
       T[GN2] = gnc;
       T[F] = fc;
       const bool not_impr = !accept && fails >= a.max_fail;
-      int rc = 0;
-      if (accept && sqrt(gnc) <= T[GTOL]) rc = 4;
-      if (accept && fabs(fc - f) <= T[LTOL]) rc = 3;
-      if (not_impr) rc = 2;
-      if ((accept || not_impr) && it >= a.max_iter) rc = 1;
+      const int rc = tron_reason(accept, not_impr, gnc, T[GTOL], fc, f, T[LTOL], it, a.max_iter);
       TI[0] = it;
       TI[1] = fails;
       if (rc > 0) { TI[2] = rc; TI[3] = 0; }
@@ -2291,9 +1827,9 @@ int pml_re_tron_csr(const int* order, int n_launch, const long long* row_ptr, co
   if (smem > 160 * 1024) return -22;
   ReTronArgs a{order, n_launch, row_ptr, col_ptr, nip, lcol, val, y, off, wt, scr, n_rows, W, f, iters, reason,
                zout, npass, loss, l2, tol, max_iter, max_fail, max_cg, dmax};
-  if (loss == LOSS_LOGISTIC) hipLaunchKernelGGL(re_tron_csr_kernel<0>, dim3(n_launch), dim3(RE_THREADS), smem, st, a);
-  else if (loss == LOSS_POISSON) hipLaunchKernelGGL(re_tron_csr_kernel<1>, dim3(n_launch), dim3(RE_THREADS), smem, st, a);
-  else hipLaunchKernelGGL(re_tron_csr_kernel<2>, dim3(n_launch), dim3(RE_THREADS), smem, st, a);
+  with_loss(loss, [&](auto L) {
+    hipLaunchKernelGGL((re_tron_csr_kernel<L()>), dim3(n_launch), dim3(RE_THREADS), smem, st, a);
+  });
   LAUNCH_CHECK();
   return 0;
 }
@@ -2314,11 +1850,9 @@ int pml_re_tron_csr_shift(const int* order, int n_launch, const long long* row_p
                zout, npass, loss, l2, tol, max_iter, max_fail, max_cg, dmax};
   a.nc = nc;
   a.ni0 = ni0;
-  if (loss == LOSS_LOGISTIC)
-    hipLaunchKernelGGL((re_tron_csr_kernel<0, true>), dim3(n_launch), dim3(RE_THREADS), smem, st, a);
-  else if (loss == LOSS_POISSON)
-    hipLaunchKernelGGL((re_tron_csr_kernel<1, true>), dim3(n_launch), dim3(RE_THREADS), smem, st, a);
-  else hipLaunchKernelGGL((re_tron_csr_kernel<2, true>), dim3(n_launch), dim3(RE_THREADS), smem, st, a);
+  with_loss(loss, [&](auto L) {
+    hipLaunchKernelGGL((re_tron_csr_kernel<L(), true>), dim3(n_launch), dim3(RE_THREADS), smem, st, a);
+  });
   LAUNCH_CHECK();
   return 0;
 }
@@ -2361,16 +1895,10 @@ int pml_re_lbfgs_csr(const int* order, int n_launch, const long long* row_ptr, c
                  zout, npass, loss, l2, tol, max_iter, 0, 0, dmax},
                 l1, m, max_ls, hist, ticket};
   const dim3 g(n_launch < grid ? n_launch : grid), b(RE_THREADS);
-#define RL_LAUNCH(L)                                                                       \
-  do {                                                                                     \
-    if (l1 > 0.0) hipLaunchKernelGGL((re_lbfgs_csr_kernel<L, true>), g, b, smem, st, p);   \
-    else hipLaunchKernelGGL((re_lbfgs_csr_kernel<L, false>), g, b, smem, st, p);           \
-  } while (0)
-  if (loss == LOSS_LOGISTIC) RL_LAUNCH(0);
-  else if (loss == LOSS_POISSON) RL_LAUNCH(1);
-  else if (loss == LOSS_SQUARED) RL_LAUNCH(2);
-  else RL_LAUNCH(3);
-#undef RL_LAUNCH
+  with_loss<4>(loss, [&](auto L) {
+    if (l1 > 0.0) hipLaunchKernelGGL((re_lbfgs_csr_kernel<L(), true>), g, b, smem, st, p);
+    else hipLaunchKernelGGL((re_lbfgs_csr_kernel<L(), false>), g, b, smem, st, p);
+  });
   LAUNCH_CHECK();
   return 0;
 }
@@ -2391,15 +1919,10 @@ int pml_re_tron_lean(const int* order, int n_launch, const long long* row_ptr, c
   ReTronArgs a{order, n_launch, row_ptr, col_ptr, nip, lcol, val, y, off, wt, scr, n_rows, W, f, iters, reason,
                zout, npass, loss, l2, tol, max_iter, max_fail, max_cg, dmax, gsc, xf2};
   // quad: every row padded to a multiple of 4 entries (row_pass_q), else the strided row_pass
-  if (quad) {
-    if (loss == LOSS_LOGISTIC) lean_launch<0, true>(a, n_launch, smem, st);
-    else if (loss == LOSS_POISSON) lean_launch<1, true>(a, n_launch, smem, st);
-    else lean_launch<2, true>(a, n_launch, smem, st);
-  } else {
-    if (loss == LOSS_LOGISTIC) lean_launch<0, false>(a, n_launch, smem, st);
-    else if (loss == LOSS_POISSON) lean_launch<1, false>(a, n_launch, smem, st);
-    else lean_launch<2, false>(a, n_launch, smem, st);
-  }
+  with_loss(loss, [&](auto L) {
+    if (quad) lean_launch<L(), true>(a, n_launch, smem, st);
+    else lean_launch<L(), false>(a, n_launch, smem, st);
+  });
   LAUNCH_CHECK();
   return 0;
 }
@@ -2407,10 +1930,10 @@ int pml_re_tron_lean(const int* order, int n_launch, const long long* row_ptr, c
 // Tall-narrow entities (d_e <= 64): one wave (= one workgroup) per entity; LDS per workgroup.
 size_t pml_re_tron_hess_smem(int dp) {
   switch (dp / 16) {
-    case 1: return (size_t)TallCfg<1>::WORDS * sizeof(double);
-    case 2: return (size_t)TallCfg<2>::WORDS * sizeof(double);
-    case 3: return (size_t)TallCfg<3>::WORDS * sizeof(double);
-    default: return (size_t)TallCfg<4>::WORDS * sizeof(double);
+    case 1: return (size_t)TronDenseCfg<1, TallRows<1>::FH>::WORDS * sizeof(double);
+    case 2: return (size_t)TronDenseCfg<2, TallRows<2>::FH>::WORDS * sizeof(double);
+    case 3: return (size_t)TronDenseCfg<3, TallRows<3>::FH>::WORDS * sizeof(double);
+    default: return (size_t)TronDenseCfg<4, TallRows<4>::FH>::WORDS * sizeof(double);
   }
 }
 
@@ -2424,26 +1947,17 @@ int pml_re_tron_hess(const int* order, int n_launch, const long long* row_ptr, c
   const size_t smem = pml_re_tron_hess_smem(dp);
   ReTronArgs a{order, n_launch, row_ptr, col_ptr, nip, lcol, val, y, off, wt, scr, n_rows, W, f, iters, reason,
                zout, npass, loss, l2, tol, max_iter, max_fail, max_cg, dp};
-#define RT_LAUNCH_L(T, L)                                                                                  \
-  hipLaunchKernelGGL((re_tron_tall_kernel<T, L>), dim3(n_launch), dim3(64), smem, st, a)
-#define RT_LAUNCH(T)                                  \
-  do {                                                \
-    if (loss == LOSS_LOGISTIC) RT_LAUNCH_L(T, 0);     \
-    else if (loss == LOSS_POISSON) RT_LAUNCH_L(T, 1); \
-    else RT_LAUNCH_L(T, 2);                           \
-  } while (0)
-  switch (dp / 16) {
-    case 1: RT_LAUNCH(1); break;
-    case 2: RT_LAUNCH(2); break;
-    case 3: RT_LAUNCH(3); break;
-    default: RT_LAUNCH(4); break;
-  }
-#undef RT_LAUNCH
-#undef RT_LAUNCH_L
+  with_loss(loss, [&](auto L) {
+    switch (dp / 16) {
+      case 1: hipLaunchKernelGGL((re_tron_tall_kernel<1, L()>), dim3(n_launch), dim3(64), smem, st, a); break;
+      case 2: hipLaunchKernelGGL((re_tron_tall_kernel<2, L()>), dim3(n_launch), dim3(64), smem, st, a); break;
+      case 3: hipLaunchKernelGGL((re_tron_tall_kernel<3, L()>), dim3(n_launch), dim3(64), smem, st, a); break;
+      default: hipLaunchKernelGGL((re_tron_tall_kernel<4, L()>), dim3(n_launch), dim3(64), smem, st, a); break;
+    }
+  });
   LAUNCH_CHECK();
   return 0;
 }
-
 
 // Register-resident kernel: LDS per workgroup, rows per workgroup.
 static size_t res_smem(int S) {
@@ -2471,12 +1985,9 @@ int pml_re_tron_res(const int* task_ent, const int* task_t0, int n_tasks, int* t
   ReTronArgs a{nullptr, 0, row_ptr, col_ptr, nip, lcol, val, y, off, wt, nullptr, 0, W, f, iters, reason,
                zout, npass, loss, l2, tol, max_iter, max_fail, max_cg, RS_DMAX};
   ResTasks tk{ticket, task_ent, task_t0, n_tasks, bar, ws, err};
-  if (loss == LOSS_LOGISTIC)
-    hipLaunchKernelGGL((re_tron_res_kernel<RES_S, 0>), dim3(grid), dim3(RS_THREADS), smem, st, a, tk);
-  else if (loss == LOSS_POISSON)
-    hipLaunchKernelGGL((re_tron_res_kernel<RES_S, 1>), dim3(grid), dim3(RS_THREADS), smem, st, a, tk);
-  else
-    hipLaunchKernelGGL((re_tron_res_kernel<RES_S, 2>), dim3(grid), dim3(RS_THREADS), smem, st, a, tk);
+  with_loss(loss, [&](auto L) {
+    hipLaunchKernelGGL((re_tron_res_kernel<RES_S, L()>), dim3(grid), dim3(RS_THREADS), smem, st, a, tk);
+  });
   LAUNCH_CHECK();
   return 0;
 }
@@ -2500,14 +2011,15 @@ int pml_rs_tron_big(int B, int n, const double* L, const double* y, const double
   if (n < 1 || n > 192 || loss < 0 || loss > 2) return -22;
   const size_t smem = ((size_t)n * (n + 1) / 2 + n) * sizeof(double);
   if (smem > 160 * 1024) return -22;
-#define RSB(E, LS) hipLaunchKernelGGL((rs_tron_big_kernel<E, LS>), dim3(B), dim3(64), smem, st, B, n, L, y, off, wt, \
-                                      beta, f, iters, reason, zout, l2, tol, max_iter, max_fail, max_cg)
-#define RSB_E(E) do { if (loss == 0) RSB(E, 0); else if (loss == 1) RSB(E, 1); else RSB(E, 2); } while (0)
-  if (n <= 64) RSB_E(1);
-  else if (n <= 128) RSB_E(2);
-  else RSB_E(3);
-#undef RSB_E
-#undef RSB
+  with_loss(loss, [&](auto LS) {
+    auto go = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(B), dim3(64), smem, st, B, n, L, y, off, wt, beta, f, iters, reason, zout, l2,
+                         tol, max_iter, max_fail, max_cg);
+    };
+    if (n <= 64) go(rs_tron_big_kernel<1, LS()>);
+    else if (n <= 128) go(rs_tron_big_kernel<2, LS()>);
+    else go(rs_tron_big_kernel<3, LS()>);
+  });
   LAUNCH_CHECK();
   return 0;
 }

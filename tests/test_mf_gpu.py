@@ -19,8 +19,8 @@ import numpy as np
 import pytest
 import torch
 
-from mf_util import LIMITED, LOSSES, TASKS, half_case, half_mismatches, make_mf_data, mf_coordinate, oracle_half, \
-    rel_err, start_factors, with_config
+from mf_util import CONVERGED, HALF_COLS, LIMITED, LOSSES, TASKS, half_case, half_mismatches, make_mf_data, \
+    mf_coordinate, oracle_half, rel_err, start_factors, with_config
 
 pytestmark = pytest.mark.gpu
 
@@ -116,6 +116,39 @@ def _many_reference():
     assert np.array_equal(ref[0][2].numpy()[sample], it_o[sample]) and rel_err(ref[0][0].numpy()[sample],
                                                                              W_o[sample]) < 1e-9
     return data, ref
+
+
+EDGE_SIZES = [1, 15, 16, 17, 31, 32, 33, 48, 49]
+
+
+@functools.lru_cache(maxsize=None)
+def _edge_data(loss):
+    return make_mf_data(EDGE_SIZES, HALF_COLS, 3, seed=3, loss=loss)
+
+
+@pytest.mark.parametrize("loss", LOSSES)
+@pytest.mark.parametrize("K", (1, 15, 16, 17, 32))
+def test_fused_and_materialised_routes_bitwise_equal(K, loss, monkeypatch):
+    """``mf_tron_kernel`` and ``re_tron_tall_kernel`` instantiate one solver (``tron_dense_wave``) and differ only in
+    how a block of 16 rows reaches LDS, so the two routes of a coordinate agree bit for bit: factors, iteration counts
+    and reasons of all four halves of two alternations, and the scores. Row entities of 1 .. 49 rows (the 16-row
+    block edge, the second and third block of the two-block pipeline), K at both padding classes and their edges,
+    about 15 % zero-weight rows, a partial score; four trust-region iterations at small scale (every step ends on the
+    region's boundary) and up to eight at unit scale (Newton steps inside it, rejected steps)."""
+    data = _edge_data(loss)
+    ps = torch.from_numpy(0.3 * np.cos(np.arange(data.n_rows)))
+    c = mf_coordinate(data, loss, K, "cuda", alternations=2, seed=11)
+    for regime in (LIMITED, dict(CONVERGED, max_iter=8)):
+        with_config(c, regime["l2"], regime["tol"], regime["max_iter"])
+        U, V = start_factors(c, 5, regime["scale"])
+        got = {}
+        for fused in ("1", "0"):
+            monkeypatch.setenv("PML_MF_FUSED", fused)
+            m = c.update_model(c._model(U.cuda(), V.cuda()), ps)
+            got[fused] = [m.U, m.V, c.score(m)] + [t for h in c._half_raw for t in h[:2]]
+            assert len(c._half_raw) == 4 and all(int(h[0].max()) > 0 for h in c._half_raw)
+        for a, b in zip(got["1"], got["0"]):
+            assert torch.equal(a, b), (K, loss, regime["max_iter"], float((a - b).abs().max()))
 
 
 def _raw_launch(row_ptr, oid, other, W0, K, n_rows, order=None):

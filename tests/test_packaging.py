@@ -25,7 +25,8 @@ def test_pip_install_into_scratch_venv_gives_working_launchers(tmp_path):
                           cwd=tmp_path, env=env, capture_output=True, text=True, check=True).stdout.strip()
     assert site.startswith(str(venv)), site                    # the installed copy, not the checkout
     for lib in ("ops/_lib/libpml_glm.so", "ops/_lib/libpml_re.so", "ops/_lib/libpml_game.so",
-                "io/_lib/libpml_avro.so", "io/_lib/libpml_indexmap.so", "ops/csrc/glm_kernels.hip"):
+                "io/_lib/libpml_avro.so", "io/_lib/libpml_indexmap.so", "ops/csrc/glm_kernels.hip",
+                "ops/csrc/pml_device.h", "ops/csrc/tron_core.h"):
         assert os.path.exists(os.path.join(site, lib)), lib
     for cmd, flag in (("game-training", "--coordinate-configurations"), ("game-scoring", "--model-input-directory"),
                       ("photon-ml", "--training-data-directory"), ("feature-indexing", "--num-storage-partitions"),
