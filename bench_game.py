@@ -85,7 +85,10 @@ def build_parser() -> argparse.ArgumentParser:
                          "at this rate, re-weighted); < 1 trains each FE update on a row-sampled copy of the shard")
     ap.add_argument("--precision", default="bf16", choices=["bf16", "f32", "f64"],
                     help="storage precision of the fixed-effect features (accumulation and optimizer state are fp64; "
-                         "random-effect features are always fp64)")
+                         "random-effect features: --re-precision)")
+    ap.add_argument("--re-precision", default="f64", choices=["bf16", "f32", "f64"],
+                    help="storage precision of the random-effect coordinate's features (storage_precision: values "
+                         "rounded once at build, fp64 arithmetic; the fused lean TRON streams them at that width)")
     ap.add_argument("--host-data", action="store_true",
                     help="generate the synthetic data with host numpy (minutes at config 5) instead of on the device")
     ap.add_argument("--seed", type=int, default=11)
@@ -218,8 +221,10 @@ def run(args, dev, rank: int = 0, world: int = 1, data=None, t_data: float = 0.0
     coords = OrderedDict([
         ("global", FixedEffectCoordinate("global", data, FixedEffectDataConfiguration("global"), fe_cfg, task,
                                          device=dev, precision=args.precision)),
-        ("per-entity", re_cls("per-entity", data, RandomEffectDataConfiguration("entityId", "entity"), re_cfg,
-                              task, device=dev)),
+        ("per-entity", re_cls("per-entity", data,
+                              RandomEffectDataConfiguration("entityId", "entity",
+                                                            storage_precision=getattr(args, "re_precision", "f64")),
+                              re_cfg, task, device=dev)),
     ])
     if torch.cuda.is_available():
         torch.cuda.synchronize()

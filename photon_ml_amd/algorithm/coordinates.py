@@ -25,7 +25,8 @@ from ..constants import EPSILON, TaskType, VarianceComputationType
 from ..utils.timing import Timed, phase
 from ..data.game_data import GameData
 from ..data.matrix import DeviceCSR
-from ..data.random_effect import FixedEffectDataConfiguration, RandomEffectDataConfiguration, RandomEffectDataset
+from ..data.random_effect import (FixedEffectDataConfiguration, RandomEffectDataConfiguration, RandomEffectDataset,
+                                  StoragePrecisionError)
 from ..function.losses import loss_for_task
 from ..models.game import FixedEffectModel, RandomEffectModel
 from ..models.glm import Coefficients, model_for_task
@@ -315,8 +316,11 @@ class RandomEffectCoordinate(Coordinate):
                                  f"projector")
             self._check_prior_config(opt_config)                     # before the dataset is built
         with phase(f"RE {coordinate_id} build: dataset"):
-            self.dataset = RandomEffectDataset(data, data_config, self.device, dtype, entity_subset=entity_subset,
-                                               layout=layout, prior=prior, normalization=self._norm_ctx)
+            try:
+                self.dataset = RandomEffectDataset(data, data_config, self.device, dtype, entity_subset=entity_subset,
+                                                   layout=layout, prior=prior, normalization=self._norm_ctx)
+            except StoragePrecisionError as e:
+                raise ValueError(f"coordinate {coordinate_id}: {e}") from None
         self._check_intercepts()
         self.compute_variance = self.variance_type != VarianceComputationType.NONE
         self.base_offsets = torch.from_numpy(data.offsets).to(self.device)
@@ -840,6 +844,9 @@ class RandomEffectCoordinate(Coordinate):
                 out["resident"] = {"entities": r["n"], "clusters": r["clusters"], "workgroups": r["tickets"],
                                    "largest_cluster": int(k.max()), "clusters_ge8": int((k >= 8).sum()),
                                    "error_flag_checks": int(getattr(self, "_res_checks", 0))}
+        if self.data_config.storage_precision != "f64":
+            # entities whose rows the lean kernel streams at the storage precision (the others read fp64 rows)
+            out["narrow"] = 0 if fused is None else int(getattr(fused, "n_narrow", 0))
         return out
 
     def _update_components(self, comps, model, l1: float, l2: float):
@@ -1257,6 +1264,9 @@ class ShardedRandomEffectCoordinate(Coordinate):
         if normalization is not None and not normalization.is_identity:
             raise ValueError(f"coordinate {coordinate_id}: normalization of a random effect is not supported under a "
                              f"process group")
+        if data_config.storage_precision != "f64":
+            raise ValueError(f"coordinate {coordinate_id}: storage precision {data_config.storage_precision} of a "
+                             f"random effect is not supported under a process group")
         self.coordinate_id = coordinate_id
         self.data_config = data_config
         self.device = torch.device(device) if device is not None else default_device()

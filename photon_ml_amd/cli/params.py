@@ -128,9 +128,12 @@ def parse_coordinate_configuration(s: str) -> Dict[str, CoordinateConfiguration]
             int(kv["active.data.bound"]) if "active.data.bound" in kv else None,
             int(kv["passive.data.bound"]) if "passive.data.bound" in kv else None,
             float(kv["features.to.samples.ratio"]) if "features.to.samples.ratio" in kv else None,
-            INDEX_MAP)
+            INDEX_MAP, kv.get("storage.precision", "f64"))
         opt = GLMOptimizationConfiguration(oc, rc, 0.0)
     else:
+        if "storage.precision" in kv:
+            raise ValueError(f"coordinate {name}: 'storage.precision' applies to random-effect coordinates only "
+                             f"(the fixed effect takes --precision): {s}")
         dc = FixedEffectDataConfiguration(shard, min_parts)
         opt = GLMOptimizationConfiguration(oc, rc, 0.0, float(kv.get("down.sampling.rate", "1.0")))
     return {name: CoordinateConfiguration(dc, opt, weights)}
@@ -158,6 +161,8 @@ def _parse_mf_coordinate_configuration(kv: Dict[str, str], s: str) -> Dict[str, 
     for bad in ("feature.shard", "random.effect.type"):
         if bad in kv:
             raise ValueError(f"matrix-factorization coordinate configuration takes no '{bad}': {s}")
+    if "storage.precision" in kv:
+        raise ValueError(f"coordinate {kv['name']}: 'storage.precision' applies to random-effect coordinates only: {s}")
     oc, rc, weights = _optimization_of(kv)
     extra = {}
     if "mf.alternations" in kv:
@@ -208,6 +213,8 @@ def coordinate_configuration_to_string(name: str, cc: CoordinateConfiguration) -
             parts.append(f"passive.data.bound={dc.passive_data_lower_bound}")
         if dc.features_to_samples_ratio is not None:
             parts.append(f"features.to.samples.ratio={dc.features_to_samples_ratio}")
+        if dc.storage_precision != "f64":
+            parts.append(f"storage.precision={dc.storage_precision}")
     elif oc.down_sampling_rate != 1.0:
         parts.append(f"down.sampling.rate={oc.down_sampling_rate}")
     return ",".join(parts)

@@ -14,6 +14,7 @@ same greedy least-loaded bin packing as the reference partitioner (``parallel/sh
 """
 from __future__ import annotations
 
+import logging
 import math
 import os
 from dataclasses import dataclass, field
@@ -30,8 +31,29 @@ from .matrix import DeviceCSR, LabeledData
 from ..utils.timing import phase
 
 
+# storage_precision of a random-effect coordinate -> the torch type its stored feature values are rounded to
+STORAGE_PRECISIONS = {"f64": None, "f32": torch.float32, "bf16": torch.bfloat16}
+
+
+class StoragePrecisionError(ValueError):
+    """A stored value is not finite after rounding to the coordinate's storage precision."""
+
+
+def round_to_storage(v: torch.Tensor, precision: str) -> torch.Tensor:
+    """``v`` (fp64) rounded IN PLACE to the values ``precision`` represents: ``v.to(float32).to(dtype).to(float64)``,
+    two round-to-nearest-even steps, the same on every device. ``f64``: untouched."""
+    dtype = STORAGE_PRECISIONS[precision]
+    if dtype is not None and v.numel():
+        v.copy_(v.to(torch.float32).to(dtype).to(torch.float64))
+    return v
+
+
 @dataclass
 class RandomEffectDataConfiguration:
+    """``storage_precision`` (``f64`` / ``f32`` / ``bf16``): the precision the coordinate's feature values are
+    STORED at. Narrower than ``f64``, the segmented dataset rounds its values once at build (after any prior or
+    normalization fold, :func:`round_to_storage`), so every solver route trains on the same rounded features in fp64
+    arithmetic, and the fused lean TRON streams them at that width. Dense-bucket datasets ignore it."""
     random_effect_type: str
     feature_shard_id: str
     min_partitions: int = 1
@@ -39,9 +61,13 @@ class RandomEffectDataConfiguration:
     passive_data_lower_bound: Optional[int] = None
     features_to_samples_ratio: Optional[float] = None
     projector_type: ProjectorType = field(default_factory=lambda: ProjectorType())
+    storage_precision: str = "f64"
 
     def __post_init__(self):
         self.projector_type = ProjectorType.parse(self.projector_type)
+        if self.storage_precision not in STORAGE_PRECISIONS:
+            raise ValueError(f"storage precision must be one of {sorted(STORAGE_PRECISIONS)}, "
+                             f"got {self.storage_precision!r}")
         if self.active_data_upper_bound is not None and self.active_data_upper_bound <= 0:
             raise ValueError("active data upper bound must be positive")
         if self.passive_data_lower_bound is not None and self.passive_data_lower_bound < 0:
@@ -406,6 +432,10 @@ class RandomEffectDataset:
         if layout == "segmented" and pt.kind != ProjectorKind.INDEX_MAP:
             raise ValueError("the segmented random-effect layout needs the INDEX_MAP projector")
         self.layout = layout
+        if layout != "segmented" and config.storage_precision != "f64":
+            logging.getLogger(__name__).info(
+                "random effect %s: storage precision %s is ignored by the dense-bucket layout (values stay fp64)",
+                re_type, config.storage_precision)
         self.buckets = []
         self.seg = None
         wts = weight_mult * data.weights
@@ -665,6 +695,9 @@ class RandomEffectDataset:
             x_seg = sp.csr_matrix((vt.numpy(), x_seg.indices, x_seg.indptr), shape=x_seg.shape)
             dv = self.device
             self.norm = NormFold(nf.f.to(dv), None if nf.c is None else nf.c.to(dv), nf.i0.to(dv), nf.has_shift)
+        if self.config.storage_precision != "f64":
+            vt = self._round_storage(torch.from_numpy(x_seg.data.astype(np.float64)))
+            x_seg = sp.csr_matrix((vt.numpy(), x_seg.indices, x_seg.indptr), shape=x_seg.shape)
         yy = np.asarray(y, dtype=np.float64)[rows]
         ww = np.asarray(wts, dtype=np.float64)[rows]
         glm = make_glm_data(LabeledData(x_seg, yy, np.zeros(len(rows)), ww), self.device, "f64", col_windows=True)
@@ -679,6 +712,18 @@ class RandomEffectDataset:
                                     torch.from_numpy(yy).to(dev), torch.from_numpy(ww).to(dev),
                                     torch.zeros(len(rows), dtype=torch.float64, device=dev), shift=self._seg_shift(dev))
         self.d_total = d_total
+
+    def _round_storage(self, val: torch.Tensor) -> torch.Tensor:
+        """The parent CSR's values rounded in place to the configured storage precision (after the folds, before
+        anything derives from them: every solver route, the scores and the variances see the rounded features).
+        :class:`StoragePrecisionError` when a value does not stay finite."""
+        prec = self.config.storage_precision
+        round_to_storage(val, prec)
+        if val.numel() and not bool(torch.isfinite(val).all()):
+            raise StoragePrecisionError(
+                f"random effect {self.config.random_effect_type} on shard {self.config.feature_shard_id}: a feature "
+                f"value is not finite after rounding to storage precision {prec}")
+        return val
 
     def _norm_fold(self, keys: torch.Tensor, n_ent: int) -> NormFold:
         """The :class:`NormFold` of the sorted projection ``keys`` (``entity * D + feature``), on their device."""
@@ -781,6 +826,9 @@ class RandomEffectDataset:
                 self.norm = self._norm_fold(ukeys, n_ent)
                 val = val.to(torch.float64).contiguous()
                 prior_fold(nip, pos.contiguous(), val, torch.zeros_like(self.norm.f), self.norm.f.contiguous())
+        if self.config.storage_precision != "f64":
+            with phase("RE segmented: storage rounding"):
+                val = self._round_storage(val.to(torch.float64).contiguous())
         yy = torch.from_numpy(np.asarray(y, dtype=np.float64)).to(dev)[rows_t]
         ww = torch.from_numpy(np.asarray(wts, dtype=np.float64)).to(dev)[rows_t]
         sort_phase.__exit__(None, None, None)

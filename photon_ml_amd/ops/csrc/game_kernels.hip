@@ -1289,6 +1289,54 @@ __global__ __launch_bounds__(256) void csr_gather_rows_kernel(const long long* _
   }
 }
 
+// The narrow variant: rows rows[r] written straight into the lean kernel's NARROW QUAD STREAM (re_kernels.hip
+// QuadRows<ReF32> / QuadRows<ReBf16>), one pass over the parent CSR, no fp64 copy in between. optr[r] is a multiple
+// of 4 and the row spans whole quads (optr[r + 1] - optr[r] = its length rounded up to 4, or 0: the row is not in
+// this stream); a lane builds one quad from 4 consecutive parent entries (slots past the row: column 0, value +0):
+//   BF16: one 16-byte record {c0 | c1 << 16, c2 | c3 << 16, v0 | v1 << 16, v2 | v3 << 16} at orec + 16 q
+//   f32 : the 8-byte column word {c0 | c1 << 16, c2 | c3 << 16} at ocol + 8 q and 4 floats at orec + 16 q
+// (q: the quad's index in the stream; u16 entity-local columns). The values were rounded to the stored type when the
+// dataset was built, so fp64 -> f32 is exact and the bf16 bits are the f32's upper half.
+typedef unsigned gq_u2 __attribute__((ext_vector_type(2)));
+typedef unsigned gq_u4 __attribute__((ext_vector_type(4)));
+typedef float gq_f4 __attribute__((ext_vector_type(4)));
+template <bool BF16>
+__global__ __launch_bounds__(256) void csr_gather_quads_kernel(const long long* __restrict__ nip,
+                                                               const long long* __restrict__ pos,
+                                                               const double* __restrict__ val,
+                                                               const long long* __restrict__ rows, long long nr,
+                                                               const long long* __restrict__ optr,
+                                                               const long long* __restrict__ cbase,
+                                                               gq_u2* __restrict__ ocol, void* __restrict__ orec) {
+  const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  if (r >= nr) return;
+  const long long dst = optr[r] >> 2, nq = (optr[r + 1] >> 2) - dst;
+  if (nq <= 0) return;
+  const long long src = nip[rows[r]], len = nip[rows[r] + 1] - src;
+  const long long base = cbase[r];
+  for (long long q = lane; q < nq; q += 64) {
+    unsigned c[4], b[4];
+    float v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const long long t = 4 * q + k;
+      const bool in = t < len;
+      c[k] = in ? (unsigned)(pos[src + t] - base) & 0xFFFFu : 0u;
+      v[k] = in ? (float)val[src + t] : 0.0f;
+      b[k] = __float_as_uint(v[k]);
+    }
+    const gq_u2 cw{c[0] | (c[1] << 16), c[2] | (c[3] << 16)};
+    if (BF16) {
+      ((gq_u4*)orec)[dst + q] =
+          gq_u4{cw.x, cw.y, (b[0] >> 16) | (b[1] & 0xFFFF0000u), (b[2] >> 16) | (b[3] & 0xFFFF0000u)};
+    } else {
+      ocol[dst + q] = cw;
+      ((gq_f4*)orec)[dst + q] = gq_f4{v[0], v[1], v[2], v[3]};
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Prior fold (incremental training, data/random_effect.py): a Gaussian prior N(mu_j, sigma_j^2) per packed
 // coefficient becomes plain L2 on column-scaled data with shifted offsets (w = mu + sigma v). One pass over the
@@ -2288,6 +2336,24 @@ int pml_csr_gather_rows(int c16, const long long* nip, const long long* pos, con
   else
     hipLaunchKernelGGL(csr_gather_rows_kernel<long long>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream,
                        nip, pos, val, rows, nr, optr, cbase, (long long*)ocol, oval);
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// the narrow quad stream (csr_gather_quads_kernel) of rows[nr] of (nip, pos, val) at optr (multiples of 4) minus
+// cbase: bf16 records in orec (ocol unused), or f32 values in orec with their u16 columns in ocol
+int pml_csr_gather_quads(int bf16, const long long* nip, const long long* pos, const double* val,
+                         const long long* rows, long long nr, const long long* optr, const long long* cbase,
+                         void* ocol, void* orec, void* stream) {
+  if (nr <= 0) return 0;
+  const long long blocks = (nr + 3) / 4;
+  if (blocks > 0x7fffffffLL || cbase == nullptr || orec == nullptr || (!bf16 && ocol == nullptr)) return -22;
+  if (bf16)
+    hipLaunchKernelGGL(csr_gather_quads_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, nip,
+                       pos, val, rows, nr, optr, cbase, (gq_u2*)ocol, orec);
+  else
+    hipLaunchKernelGGL(csr_gather_quads_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, nip,
+                       pos, val, rows, nr, optr, cbase, (gq_u2*)ocol, orec);
   LAUNCH_CHECK();
   return 0;
 }

@@ -80,6 +80,8 @@ struct ReTronArgs {
   const double* xf2;         // lean kernel, optional: ||X_e||_F^2 per entity (lazy zero-point gradient norm)
   const double* nc;          // re_tron_csr_kernel<LOSS, true>: shift c = f s per coefficient (packed like W)
   const int* ni0;            // re_tron_csr_kernel<LOSS, true>: entity-local intercept column per entity (c[i0] = 0)
+  const void* nrec;          // re_tron_lean_kernel<.., VT>: the narrow quad stream (QuadRows<ReF32 / ReBf16>); nip
+                             // (and lcol for f32) are then that stream's, val is unused
 };
 
 #define RE_G 16                      // lanes per row (one DPP row)
@@ -363,6 +365,186 @@ __device__ __forceinline__ void row_pass_q(const ReTronArgs& a, long long r0, lo
         atomicAdd(&acc[kt[1]], t * a0.y);
         atomicAdd(&acc[kt[2]], t * a1.x);
         atomicAdd(&acc[kt[3]], t * a1.y);
+      }
+    }
+    npr = npr_next;
+  }
+}
+
+// Quad row pass over a NARROW STORED VALUE TYPE (re_tron_lean_kernel<LOSS, J, true, ReF32 / ReBf16>). QuadRows<VT> is
+// the quad stream of the type: what a lane loads for its quad and how the quad widens to fp64. row_pass_qn is row_pass_q over
+// it: the same lane-to-quad mapping, the same order of every FMA, LDS add, row sum and combine, all in fp64 -- so on
+// values the narrow type represents exactly it gives the bits of row_pass_q, at fewer bytes and loads per quad:
+//   fp64    40 B, 3 loads: row_pass_q above
+//   ReF32   24 B, 2 loads: re_u2 {4 x u16 column} at lcol + 4 q, one re_f4 {4 x f32} at nrec + 16 q bytes
+//   ReBf16  16 B, 1 load : one re_u4 record at nrec + 16 q bytes = {c0 | c1 << 16, c2 | c3 << 16, v0 | v1 << 16,
+//                          v2 | v3 << 16} (u16 columns, bf16 values: the fused narrow records of the tiled kernels)
+// Every load is an aligned 8- or 16-byte vector load (rows start on quads; the arrays are 16-byte aligned). Widening
+// is exact: bf16 -> f32 is a 16-bit shift, f32 -> f64 one conversion; narrow quads stay narrow in registers
+// (4 / 6 VGPRs per quad in flight instead of 10) and widen at their two uses.
+struct ReF32 {};
+struct ReBf16 {};
+typedef float re_f4 __attribute__((ext_vector_type(4)));
+typedef unsigned re_u4 __attribute__((ext_vector_type(4)));
+
+template <typename VT>
+struct QuadRows;
+
+template <>
+struct QuadRows<ReF32> {
+  struct Quad { re_u2 c; re_f4 v; };
+  const re_u2* __restrict__ cq;
+  const re_f4* __restrict__ vq;
+  __device__ __forceinline__ QuadRows(const ReTronArgs& a, long long e0)
+      : cq((const re_u2*)(a.lcol + e0)), vq((const re_f4*)((const float*)a.nrec + e0)) {}
+  __device__ __forceinline__ Quad load(int q) const { return Quad{gld(cq + q), gld(vq + q)}; }
+  static __device__ __forceinline__ void widen(const Quad& t, double (&v)[4]) {
+    v[0] = (double)t.v.x; v[1] = (double)t.v.y; v[2] = (double)t.v.z; v[3] = (double)t.v.w;
+  }
+};
+
+template <>
+struct QuadRows<ReBf16> {
+  struct Quad { re_u2 c; re_u2 v; };
+  const re_u4* __restrict__ rq;
+  __device__ __forceinline__ QuadRows(const ReTronArgs& a, long long e0) : rq((const re_u4*)a.nrec + (e0 >> 2)) {}
+  __device__ __forceinline__ Quad load(int q) const {
+    const re_u4 r = gld(rq + q);
+    return Quad{re_u2{r.x, r.y}, re_u2{r.z, r.w}};
+  }
+  static __device__ __forceinline__ void widen(const Quad& t, double (&v)[4]) {
+    v[0] = (double)__uint_as_float(t.v.x << 16);
+    v[1] = (double)__uint_as_float(t.v.x & 0xFFFF0000u);
+    v[2] = (double)__uint_as_float(t.v.y << 16);
+    v[3] = (double)__uint_as_float(t.v.y & 0xFFFF0000u);
+  }
+};
+
+template <typename VT, int MODE, int LOSS, int U, int NW = RE_NW>
+__device__ __forceinline__ void row_pass_qn(const ReTronArgs& a, long long r0, long long r1,
+                                           const double* __restrict__ vec, double* __restrict__ acc,
+                                           const double* __restrict__ Dc, double* __restrict__ Dn,
+                                           double* __restrict__ Zn, double& fpart) {
+  using Rows = QuadRows<VT>;
+  using Quad = typename Rows::Quad;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int grp = lane / RE_G, gl = lane % RE_G;
+  const int nrows = (int)(r1 - r0);
+  const long long e0 = a.nip[r0];                           // a multiple of 4 (padded rows)
+  const long long* __restrict__ nip = a.nip + r0;
+  const Rows rows(a, e0);
+  const double* __restrict__ wt = a.wt + r0;
+  const double* __restrict__ off = a.off + r0;
+  const double* __restrict__ yv = a.y + r0;
+  if (MODE == 0) Dc += r0;
+  if (MODE == 1) { Dn += r0; Zn += r0; }
+  constexpr int BATCH = RE_RPI * U;
+  const int step = NW * BATCH;
+  int base = w * BATCH;
+  // row pointers of a batch, in quads: lane j <= BATCH holds nip[base + j] / 4 (prefetched as in row_pass)
+  auto fetch_raw = [&](int b) -> long long {
+    const int i = b + (lane <= BATCH ? lane : BATCH);
+    return gld(nip + (i < nrows ? i : nrows));
+  };
+  auto cols = [](re_u2 c, int (&k)[4]) {
+    k[0] = (int)(c.x & 0xFFFFu); k[1] = (int)(c.x >> 16); k[2] = (int)(c.y & 0xFFFFu); k[3] = (int)(c.y >> 16);
+  };
+  long long npr = fetch_raw(base);
+  for (; base < nrows; base += step) {
+    const int np = (int)((npr - e0) >> 2);
+    const long long npr_next = fetch_raw(base + step);
+    int qa[U], qb[U];
+    Quad qd[U];
+    double dot[U], rs[U][3];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int q = u * RE_RPI + grp;
+      qa[u] = __shfl(np, q, 64) + gl;                         // this lane's quad
+      qb[u] = __shfl(np, q + 1, 64);                          // the row's end (quads)
+      const int i = base + q;
+      const bool valid = i < nrows;
+      const int ic = valid ? i : 0;
+      if (MODE == 0) {
+        rs[u][0] = valid ? gld(Dc + ic) : 0.0;
+      } else {
+        rs[u][0] = valid ? gld(wt + ic) : 0.0;
+        rs[u][1] = valid ? gld(off + ic) : 0.0;
+        rs[u][2] = valid ? gld(yv + ic) : 0.0;
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const bool in = qa[u] < qb[u];
+      const int qq = in ? qa[u] : 0;
+      qd[u] = rows.load(qq);
+      if (!in) qd[u] = Quad{};
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      double s = 0.0;
+      if (MODE != 2) {
+        int k[4];
+        cols(qd[u].c, k);
+        double g[4], v[4];
+        lds_gather4(vec, k[0], k[1], k[2], k[3], g[0], g[1], g[2], g[3]);
+        Rows::widen(qd[u], v);
+        s = fma(v[0], g[0], s);
+        s = fma(v[1], g[1], s);
+        s = fma(v[2], g[2], s);
+        s = fma(v[3], g[3], s);
+        for (int qq = qa[u] + RE_G; qq < qb[u]; qq += RE_G) {     // rows longer than 64 entries
+          const Quad t = rows.load(qq);
+          int kt[4];
+          cols(t.c, kt);
+          double tv[4];
+          Rows::widen(t, tv);
+          s = fma(tv[0], vec[kt[0]], s);
+          s = fma(tv[1], vec[kt[1]], s);
+          s = fma(tv[2], vec[kt[2]], s);
+          s = fma(tv[3], vec[kt[3]], s);
+        }
+      }
+      dot[u] = s;
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if (MODE != 2) dot[u] = row16_total(dot[u]);
+      const int i = base + u * RE_RPI + grp;
+      const bool valid = i < nrows;
+      double t;
+      if (MODE == 0) {
+        t = rs[u][0] * dot[u];
+      } else {
+        double l = 0.0, dl = 0.0, d2 = 0.0;
+        if (valid) {
+          loss_t<LOSS>(dot[u] + rs[u][1], rs[u][2], l, dl, d2);
+          if (gl == 0) {
+            fpart += wx(rs[u][0], l);
+            if (MODE == 1) { Dn[i] = wx(rs[u][0], d2); Zn[i] = dot[u]; }
+          }
+        }
+        t = wx(rs[u][0], dl);
+      }
+      if (qa[u] < qb[u]) {
+        int k[4];
+        cols(qd[u].c, k);
+        double v[4];
+        Rows::widen(qd[u], v);
+        atomicAdd(&acc[k[0]], t * v[0]);
+        atomicAdd(&acc[k[1]], t * v[1]);
+        atomicAdd(&acc[k[2]], t * v[2]);
+        atomicAdd(&acc[k[3]], t * v[3]);
+      }
+      for (int qq = qa[u] + RE_G; qq < qb[u]; qq += RE_G) {
+        const Quad tq = rows.load(qq);
+        int kt[4];
+        cols(tq.c, kt);
+        double tv[4];
+        Rows::widen(tq, tv);
+        atomicAdd(&acc[kt[0]], t * tv[0]);
+        atomicAdd(&acc[kt[1]], t * tv[1]);
+        atomicAdd(&acc[kt[2]], t * tv[2]);
+        atomicAdd(&acc[kt[3]], t * tv[3]);
       }
     }
     npr = npr_next;
@@ -875,10 +1057,12 @@ __global__ __launch_bounds__(RE_THREADS) void re_lbfgs_csr_kernel(ReLbfgsArgs p)
 #endif
 #define LEAN_THREADS (LEAN_NW * 64)
 // row pass of the lean kernel: quads over padded rows (Q) or the strided row_pass
-template <bool Q, int MODE, int LOSS, int U>
+template <bool Q, int MODE, int LOSS, int U, typename VT>
 __device__ __forceinline__ void lean_pass(const ReTronArgs& a, long long r0, long long r1, const double* vec,
                                           double* acc, const double* Dc, double* Dn, double* Zn, double& fpart) {
-  if constexpr (Q) row_pass_q<MODE, LOSS, U, LEAN_NW>(a, r0, r1, vec, acc, Dc, Dn, Zn, fpart);
+  if constexpr (Q && !std::is_same<VT, double>::value)
+    row_pass_qn<VT, MODE, LOSS, U, LEAN_NW>(a, r0, r1, vec, acc, Dc, Dn, Zn, fpart);
+  else if constexpr (Q) row_pass_q<MODE, LOSS, U, LEAN_NW>(a, r0, r1, vec, acc, Dc, Dn, Zn, fpart);
   else row_pass<MODE, LOSS, U, LEAN_NW>(a, r0, r1, vec, acc, Dc, Dn, Zn, fpart);
 }
 #ifndef LEAN_WPE
@@ -890,7 +1074,10 @@ __device__ __forceinline__ void lean_pass(const ReTronArgs& a, long long r0, lon
 #ifndef LEAN_UH
 #define LEAN_UH 3
 #endif
-template <int LOSS, int J, bool Q>
+// VT: the stored value type of the rows. double: a.nip / a.lcol / a.val, as every other kernel reads them. ReF32 /
+// ReBf16 (Q only): a narrow quad stream (QuadRows<VT>) -- a.nip and a.nrec, with a.lcol for ReF32, are the stream's
+// and rows are always whole quads; every other array (row_ptr, y, wt, off, scr, W, gsc, xf2) is the batch's.
+template <int LOSS, int J, bool Q, typename VT = double>
 __global__ __launch_bounds__(LEAN_THREADS) __attribute__((amdgpu_waves_per_eu(LEAN_WPE, LEAN_WPE)))
 void re_tron_lean_kernel(ReTronArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -923,8 +1110,8 @@ void re_tron_lean_kernel(ReTronArgs a) {
     __syncthreads();
     for (int j = lane; j < d; j += 64) myacc[j] = 0.0;
     double fp = 0.0;
-    if (at_zero) lean_pass<Q, 2, LOSS, LEAN_UF>(a, r0, r1, sD, myacc, nullptr, nullptr, nullptr, fp);
-    else lean_pass<Q, 1, LOSS, LEAN_UF>(a, r0, r1, sD, myacc, nullptr, D[nb], Z[nb], fp);
+    if (at_zero) lean_pass<Q, 2, LOSS, LEAN_UF, VT>(a, r0, r1, sD, myacc, nullptr, nullptr, nullptr, fp);
+    else lean_pass<Q, 1, LOSS, LEAN_UF, VT>(a, r0, r1, sD, myacc, nullptr, D[nb], Z[nb], fp);
     __syncthreads();
     double s3[3] = {fp, 0.0, 0.0};
 #pragma unroll
@@ -1011,7 +1198,7 @@ void re_tron_lean_kernel(ReTronArgs a) {
       __syncthreads();
       for (int j = lane; j < d; j += 64) myacc[j] = 0.0;
       double fp = 0.0;
-      lean_pass<Q, 0, LOSS, LEAN_UH>(a, r0, r1, sD, myacc, D[cur], nullptr, nullptr, fp);
+      lean_pass<Q, 0, LOSS, LEAN_UH, VT>(a, r0, r1, sD, myacc, D[cur], nullptr, nullptr, fp);
       __syncthreads();
       double s5[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
       double H[J];
@@ -1809,6 +1996,15 @@ static void lean_launch(const ReTronArgs& a, int n_launch, size_t smem, hipStrea
   else hipLaunchKernelGGL((re_tron_lean_kernel<LOSS, 4, Q>), dim3(n_launch), dim3(LEAN_THREADS), smem, st, a);
 }
 
+template <int LOSS, typename VT>
+static void lean_narrow_launch(const ReTronArgs& a, int n_launch, size_t smem, hipStream_t st) {
+  if (a.dmax <= LEAN_THREADS)
+    hipLaunchKernelGGL((re_tron_lean_kernel<LOSS, 1, true, VT>), dim3(n_launch), dim3(LEAN_THREADS), smem, st, a);
+  else if (a.dmax <= 2 * LEAN_THREADS)
+    hipLaunchKernelGGL((re_tron_lean_kernel<LOSS, 2, true, VT>), dim3(n_launch), dim3(LEAN_THREADS), smem, st, a);
+  else hipLaunchKernelGGL((re_tron_lean_kernel<LOSS, 4, true, VT>), dim3(n_launch), dim3(LEAN_THREADS), smem, st, a);
+}
+
 extern "C" {
 
 const char* pml_build_id() { return pml_build_stamp + 13; }
@@ -1912,15 +2108,22 @@ int pml_re_tron_lean(const int* order, int n_launch, const long long* row_ptr, c
                      const double* off, const double* wt, double* scr, long long n_rows, double* W, double* f,
                      int* iters, int* reason, double* zout, int* npass, int loss, double l2, double tol,
                      int max_iter, int max_fail, int max_cg, int dmax, double* gsc, int quad, const double* xf2,
-                     hipStream_t st) {
+                     int vtype, const void* nrec, hipStream_t st) {
   if (n_launch <= 0) return 0;
   if (dmax <= 0 || dmax > 1024 || loss < 0 || loss > 2 || gsc == nullptr) return -22;
+  // vtype: the stored value type of the rows. 0 = fp64 (lcol / val); 1 = f32, 2 = bf16: a narrow quad stream
+  // (QuadRows<ReF32> / QuadRows<ReBf16>) in nrec whose row pointer is nip (f32: its columns in lcol), always quads
+  if (vtype < 0 || vtype > 2 || (vtype != 0 && (nrec == nullptr || !quad)) || (vtype == 1 && lcol == nullptr))
+    return -22;
   const size_t smem = pml_re_tron_lean_smem(dmax);
   ReTronArgs a{order, n_launch, row_ptr, col_ptr, nip, lcol, val, y, off, wt, scr, n_rows, W, f, iters, reason,
                zout, npass, loss, l2, tol, max_iter, max_fail, max_cg, dmax, gsc, xf2};
+  a.nrec = nrec;
   // quad: every row padded to a multiple of 4 entries (row_pass_q), else the strided row_pass
   with_loss(loss, [&](auto L) {
-    if (quad) lean_launch<L(), true>(a, n_launch, smem, st);
+    if (vtype == 1) lean_narrow_launch<L(), ReF32>(a, n_launch, smem, st);
+    else if (vtype == 2) lean_narrow_launch<L(), ReBf16>(a, n_launch, smem, st);
+    else if (quad) lean_launch<L(), true>(a, n_launch, smem, st);
     else lean_launch<L(), false>(a, n_launch, smem, st);
   });
   LAUNCH_CHECK();

@@ -814,6 +814,8 @@ def game_lib() -> Optional[ctypes.CDLL]:
         lib.pml_csr_gather_rows.argtypes = [c_int, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_longlong,
                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
         lib.pml_csr_gather_rows.restype = c_int
+        lib.pml_csr_gather_quads.argtypes = lib.pml_csr_gather_rows.argtypes
+        lib.pml_csr_gather_quads.restype = c_int
         lib.pml_key_hist.argtypes = [c_int, c_void_p, ctypes.c_longlong, ctypes.c_longlong, c_void_p, c_void_p]
         lib.pml_key_hist.restype = c_int
         lib.pml_prior_fold.argtypes = [c_void_p, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p,
@@ -916,6 +918,73 @@ def csr_gather_rows(nip: torch.Tensor, pos: torch.Tensor, val: torch.Tensor, row
         optr.data_ptr(), None if cbase is None else cbase.data_ptr(), ocol.data_ptr(), oval.data_ptr(),
         stream_handle(dev)), "csr_gather_rows")
     return ocol, oval
+
+
+def csr_gather_quads(nip: torch.Tensor, pos: torch.Tensor, val: torch.Tensor, rows: torch.Tensor, optr: torch.Tensor,
+                     cbase: torch.Tensor, precision: str):
+    """Rows ``rows`` of the CSR ``(nip, pos, val)`` as the lean kernel's narrow quad stream
+    (``csr_gather_quads_kernel``, device only): row r starts at ``optr[r]`` (a multiple of 4) and spans its length
+    rounded up to 4 (padding: column 0 / value +0), or nothing (``optr[r + 1] == optr[r]``: not in this stream).
+    ``val`` must already hold values of ``precision`` (the conversion is then exact). Returns ``(cols, rec)``:
+    ``f32``: int16 entity-local columns and float32 values, one per slot; ``bf16``: ``cols`` None and ``rec`` int32,
+    four words per quad ``{c0 | c1 << 16, c2 | c3 << 16, v0 | v1 << 16, v2 | v3 << 16}``."""
+    assert precision in ("f32", "bf16")
+    nr = int(rows.numel())
+    total = int(optr[-1]) if nr else 0
+    dev = val.device
+    assert dev.type == "cuda" and optr.numel() == nr + 1 and total % 4 == 0
+    for t_ in (nip, pos, rows, optr, cbase):
+        assert t_.dtype == torch.int64 and t_.is_cuda and t_.is_contiguous()
+    assert val.dtype == torch.float64 and val.is_contiguous()
+    # One zero quad behind the stream (4 elements of either array are one quad: 4 int32 = a 16-byte bf16 record, 4
+    # floats / 4 int16 = an f32 quad's values / columns). A lane without a quad of its own reads its entity's first
+    # quad (``rows.load(0)`` in row_pass_qn); for a trailing entity without entries that is exactly this quad, which
+    # would otherwise lie past the allocation. The returned slices share, and keep alive, the padded storage.
+    cols = torch.zeros(total + 4, dtype=torch.int16, device=dev)[:total] if precision == "f32" else None
+    rec = torch.zeros(total + 4, dtype=torch.float32 if precision == "f32" else torch.int32, device=dev)[:total]
+    if nr and total:
+        check(require_game_lib().pml_csr_gather_quads(
+            int(precision == "bf16"), nip.data_ptr(), pos.data_ptr(), val.data_ptr(), rows.data_ptr(), nr,
+            optr.data_ptr(), cbase.data_ptr(), None if cols is None else cols.data_ptr(), rec.data_ptr(),
+            stream_handle(dev)), "csr_gather_quads")
+    return cols, rec
+
+
+def narrow_quad_parts(precision: str, cols: Optional[torch.Tensor], rec: torch.Tensor):
+    """``(columns int64, values fp64)`` per slot of a narrow quad stream (:func:`csr_gather_quads`), widened: a
+    temporary for host-side checks and ``||X_e||_F^2``, never kept."""
+    if precision == "f32":
+        return cols.to(torch.int64) & 0xFFFF, rec.to(torch.float64)
+    h = rec.view(torch.int16).view(-1, 8)          # per quad: c0 c1 c2 c3 | v0 v1 v2 v3 (16-bit halves)
+    return (h[:, :4].reshape(-1).to(torch.int64) & 0xFFFF,
+            h[:, 4:].contiguous().view(torch.bfloat16).reshape(-1).to(torch.float64))
+
+
+def check_re_narrow_inputs(row_ptr: torch.Tensor, col_ptr: torch.Tensor, nip: torch.Tensor, precision: str,
+                           cols: Optional[torch.Tensor], rec: torch.Tensor) -> None:
+    """Host-side check of what the narrow lean kernels index by (``PML_CHECK_KERNEL_INPUTS=1``): the stream's row
+    pointer runs from 0 to its number of slots in multiples of 4 without decreasing, and every entity-local column
+    is below its entity's width. Raises ValueError; nothing is launched."""
+    n_rows = int(row_ptr[-1])
+    if nip.numel() != n_rows + 1 or rec.numel() % 4 or (cols is not None and cols.numel() != rec.numel()):
+        raise ValueError(f"narrow rows: {nip.numel()} row pointers for {n_rows} rows, {rec.numel()} slots")
+    if bool((nip % 4 != 0).any()):
+        raise ValueError("narrow rows: every row must start on a quad and hold whole quads (row pointer entries "
+                         "must be multiples of 4)")
+    if int(nip[0]) != 0 or int(nip[-1]) != rec.numel() or bool((nip[1:] < nip[:-1]).any()):
+        raise ValueError(f"narrow rows: row pointer must run from 0 to {rec.numel()} without decreasing")
+    if not rec.numel():
+        return
+    c, _ = narrow_quad_parts(precision, cols, rec)
+    n_ent = row_ptr.numel() - 1
+    row_ent = torch.repeat_interleave(torch.arange(n_ent, device=nip.device), row_ptr[1:] - row_ptr[:-1],
+                                      output_size=n_rows)
+    d_slot = torch.repeat_interleave((col_ptr[1:] - col_ptr[:-1])[row_ent], nip[1:] - nip[:-1],
+                                     output_size=rec.numel())
+    bad = c >= d_slot
+    if bool(bad.any()):
+        k = int(torch.nonzero(bad)[0])
+        raise ValueError(f"narrow rows: local column {int(c[k])} at slot {k} outside [0, {int(d_slot[k])})")
 
 
 def check_prior_fold_inputs(nip: torch.Tensor, pos: torch.Tensor, val: torch.Tensor, mu: torch.Tensor,
@@ -1617,7 +1686,8 @@ def re_lib() -> Optional[ctypes.CDLL]:
         lib.pml_re_tron_smem.argtypes = [c_int]
         lib.pml_re_tron_smem.restype = ctypes.c_size_t
         lib.pml_re_tron_hess.argtypes = lib.pml_re_tron_csr.argtypes
-        lib.pml_re_tron_lean.argtypes = lib.pml_re_tron_csr.argtypes[:-1] + [c_void_p, c_int, c_void_p, c_void_p]
+        lib.pml_re_tron_lean.argtypes = lib.pml_re_tron_csr.argtypes[:-1] + [c_void_p, c_int, c_void_p, c_int,
+                                                                             c_void_p, c_void_p]
         lib.pml_re_tron_lean.restype = c_int
         lib.pml_re_tron_hess.restype = c_int
         lib.pml_re_tron_hess_smem.argtypes = [c_int]
@@ -1690,7 +1760,7 @@ def re_tron_csr(order, row_ptr, col_ptr, nip, lcol, val, y, off, wt, scr, W, f, 
                 l2: float, tol: float, max_iter: int, max_fail: int, max_cg: int, dmax: int,
                 npass: Optional[torch.Tensor] = None, hessian: bool = False, gsc: Optional[torch.Tensor] = None,
                 lean: Optional[bool] = None, quad: bool = False, xf2: Optional[torch.Tensor] = None,
-                shift=None) -> None:
+                shift=None, narrow=None) -> None:
     """Fused per-entity primal TRON over the entities ``order`` (int32; one workgroup each) of a block-diagonal
     CSR (``re_tron_csr_kernel``). Entity ``e`` owns rows ``row_ptr[e]:row_ptr[e+1]`` (int64) and coefficients
     ``col_ptr[e]:col_ptr[e+1]`` of the packed ``W`` (fp64, in: warm start, out: solution); ``nip`` int64 row
@@ -1706,7 +1776,10 @@ def re_tron_csr(order, row_ptr, col_ptr, nip, lcol, val, y, off, wt, scr, W, f, 
     ``||X_e||_F ||c||`` of ``||g(0)||`` and runs the pass at zero only if a gradient norm reaches it. ``shift`` =
     ``(c, i0)`` (fp64 packed like ``W``; int32 per entity, the entity-local intercept column): the entity's design
     matrix is ``X (I - e_i0 c^T)`` (``re_tron_csr_kernel<LOSS, true>``: the streaming kernel only, not ``hessian``
-    / ``lean``). Device only; in place, nothing returned."""
+    / ``lean``). ``narrow`` = ``(precision, nip, cols, rec)`` (lean only): the launch reads its rows from this narrow
+    quad stream (:func:`csr_gather_quads`; ``precision`` ``"f32"`` / ``"bf16"``, ``nip`` int64 over the same rows in
+    multiples of 4) with ``re_tron_lean_kernel<LOSS, J, true, VT>`` instead of ``nip`` / ``lcol`` / ``val``. Device
+    only; in place, nothing returned."""
     if shift is not None:
         if hessian or lean:
             raise ValueError("re_tron_csr: a shift runs on the streaming kernel only (not hessian / lean)")
@@ -1756,8 +1829,25 @@ def re_tron_csr(order, row_ptr, col_ptr, nip, lcol, val, y, off, wt, scr, W, f, 
         assert gsc.is_cuda and gsc.dtype == torch.float64 and gsc.numel() >= W.numel() and gsc.device == W.device
         if xf2 is not None:
             assert xf2.is_cuda and xf2.dtype == torch.float64 and xf2.numel() == n_ent and xf2.is_contiguous()
-        check(lib.pml_re_tron_lean(*args, gsc.data_ptr(), int(bool(quad)), None if xf2 is None else xf2.data_ptr(),
-                                   stream_handle(W.device)), "re_tron_lean")
+        xf2_p = None if xf2 is None else xf2.data_ptr()
+        if narrow is not None:
+            prec, n_nip, n_cols, n_rec = narrow
+            assert prec in ("f32", "bf16")
+            assert n_nip.is_cuda and n_nip.dtype == torch.int64 and n_nip.is_contiguous()
+            assert n_nip.numel() == n_rows + 1
+            assert n_rec.is_cuda and n_rec.is_contiguous() and n_rec.device == W.device and n_rec.numel() % 4 == 0
+            assert n_rec.dtype == (torch.float32 if prec == "f32" else torch.int32) and n_rec.data_ptr() % 16 == 0
+            if prec == "f32":
+                assert n_cols.is_cuda and n_cols.dtype == torch.int16 and n_cols.is_contiguous()
+                assert n_cols.numel() == n_rec.numel() and n_cols.data_ptr() % 8 == 0
+            if os.environ.get("PML_CHECK_KERNEL_INPUTS", "0") == "1":
+                check_re_narrow_inputs(row_ptr, col_ptr, n_nip, prec, n_cols, n_rec)
+            args[4:7] = [n_nip.data_ptr(), n_cols.data_ptr() if prec == "f32" else None, None]
+            check(lib.pml_re_tron_lean(*args, gsc.data_ptr(), 1, xf2_p, 1 if prec == "f32" else 2, n_rec.data_ptr(),
+                                       stream_handle(W.device)), "re_tron_lean")
+            return
+        check(lib.pml_re_tron_lean(*args, gsc.data_ptr(), int(bool(quad)), xf2_p, 0, None, stream_handle(W.device)),
+              "re_tron_lean")
         return
     if shift is not None:
         for t in (sc, si0):
@@ -1767,6 +1857,7 @@ def re_tron_csr(order, row_ptr, col_ptr, nip, lcol, val, y, off, wt, scr, W, f, 
         check(lib.pml_re_tron_csr_shift(*args, sc.data_ptr(), si0.data_ptr(), stream_handle(W.device)),
               "re_tron_csr_shift")
         return
+    assert narrow is None, "a narrow quad stream is read by the lean kernel only"
     fn = lib.pml_re_tron_hess if hessian else lib.pml_re_tron_csr
     check(fn(*args, stream_handle(W.device)), "re_tron_csr")
 

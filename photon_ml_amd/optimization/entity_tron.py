@@ -112,7 +112,15 @@ class EntityTronBatch:
 
     When the data carries a normalization shift (``seg.shift``) every class, dm <= 1024 included, launches
     ``re_tron_csr_kernel<LOSS, true>`` with the batch's own ``c`` (gathered by ``cols``) and per-entity intercept
-    column; the lean, tall, Hessian and resident kernels are never launched."""
+    column; the lean, tall, Hessian and resident kernels are never launched.
+
+    Narrow storage (``ds.config.storage_precision`` ``f32`` / ``bf16``, GPU, no shift): the gathered copy is split in
+    two complementary streams over the same batch rows. The LEAN entities (64 < d_e <= ``RE_LEAN_DMAX``, not
+    register-resident) have their rows in ``self.narrow`` only -- a quad stream of the stored type
+    (``ops.native.csr_gather_quads``), always whole quads -- and length 0 in ``self.nip``; every other entity keeps
+    fp64 rows in ``self.nip`` / ``lcol`` / ``val`` as at ``f64`` and has length 0 in the narrow row pointer. Lean
+    launches read the narrow stream (``re_tron_lean_kernel<LOSS, J, true, VT>``), all others the fp64 one; ``row_ptr``,
+    ``y``, ``w``, offsets, ``scr``, ``z`` and ``gsc`` are shared. :meth:`stream_bytes` reports what each stream holds."""
 
     def __init__(self, ds, mask: torch.Tensor):
         seg = ds.seg
@@ -147,6 +155,8 @@ class EntityTronBatch:
                 self.n_heavy = int(heavy.sum())
                 sel &= ~heavy
         self.mask = sel
+        self.narrow = None                             # (precision, nip, cols, rec) of the lean entities' rows
+        self.n_narrow = 0
         self.ents = torch.nonzero(sel).squeeze(1)
         self.B = int(self.ents.numel())
         self.W: Optional[torch.Tensor] = None          # last solution (warm start of the next solve)
@@ -161,6 +171,11 @@ class EntityTronBatch:
         self.col_ptr = torch.zeros(self.B + 1, dtype=torch.int64, device=dev)
         torch.cumsum(de, 0, out=self.col_ptr[1:])
         n_rows = int(self.row_ptr[-1])
+        row_ent = torch.repeat_interleave(torch.arange(self.B, device=dev), ne, output_size=n_rows)
+        # Entities of at most HESS_DMAX coefficients (tall: the row space took the wide ones) run the exact-Hessian
+        # kernel (MFMA), the others the sparse Hessian-vector kernel.
+        hess = (de <= HESS_DMAX) & (not shifted)
+        stream_sel = ~hess
         if dev.type == "cuda":
             # the batch's rows straight from the parent CSR by one gather kernel (entity-local int16 columns, rows
             # padded to whole quads when the lean kernel reads quads): no nnz-sized torch index / scatter chain
@@ -172,17 +187,40 @@ class EntityTronBatch:
             self.quad = (nnz > 0 and nnz >= QUAD_MIN_ROW_NNZ * n_rows and os.environ.get("PML_RE_QUAD", "1") != "0"
                          and not bool((de <= HESS_DMAX).any()) and not shifted)
             plen = (row_nnz + 3) // 4 * 4 if self.quad else row_nnz
+            cbase = seg.col_ptr[seg.row_entity[row_sel]]               # parent column of the entity's local 0
+            # slots per entity as gathered, and (before the gather: a narrow batch keeps them in the fp64 stream) the
+            # register-resident entities
+            ent_nnz = torch.zeros(self.B, dtype=torch.int64, device=dev).index_add_(0, row_ent, plen)
+            res_sel = None if shifted else self._resident_mask(ne, de, ent_nnz, row_ent, row_nnz, stream_sel)
+            prec = getattr(getattr(ds, "config", None), "storage_precision", "f64")
+            if prec != "f64" and not shifted:
+                # narrow storage: the lean entities' rows leave the fp64 stream for a quad stream of the stored type
+                from ..ops.native import RE_LEAN_DMAX, csr_gather_quads
+                lean_e = stream_sel & (de <= RE_LEAN_DMAX)
+                if res_sel is not None:
+                    lean_e &= ~res_sel[0]
+                if bool(lean_e.any()):
+                    lean_r = lean_e[row_ent]
+                    zero = torch.zeros_like(plen)
+                    nlen = torch.where(lean_r, (row_nnz + 3) // 4 * 4, zero)
+                    plen = torch.where(lean_r, zero, plen)
+                    n_nip = torch.zeros(n_rows + 1, dtype=torch.int64, device=dev)
+                    torch.cumsum(nlen, 0, out=n_nip[1:])
+                    n_cols, n_rec = csr_gather_quads(pnip, ppos, pval, row_sel, n_nip, cbase, prec)
+                    self.narrow = (prec, n_nip, n_cols, n_rec)
+                    self.n_narrow = int(lean_e.sum())
+                    # the launch order sees an entity's slots in whichever stream holds them
+                    ent_nnz = torch.zeros(self.B, dtype=torch.int64, device=dev).index_add_(0, row_ent, plen + nlen)
+                    del lean_r, zero, nlen
             nip = torch.zeros(n_rows + 1, dtype=torch.int64, device=dev)
             torch.cumsum(plen, 0, out=nip[1:])
-            cbase = seg.col_ptr[seg.row_entity[row_sel]]               # parent column of the entity's local 0
             self.lcol, val = csr_gather_rows(pnip, ppos, pval, row_sel, nip, cbase, torch.int16)
             del cbase, plen
-            if os.environ.get("PML_CHECK_KERNEL_INPUTS", "0") == "1" and nnz:
+            if os.environ.get("PML_CHECK_KERNEL_INPUTS", "0") == "1" and self.lcol.numel():
                 assert int(self.lcol.min()) >= 0 and int(self.lcol.max()) < int(de.max()), "local column range"
             self.nip, self.val = nip, val
         else:
             nip, pos, val, row_sel, col_sel, _ = ds.entity_csr(sel)
-            row_ent = torch.repeat_interleave(torch.arange(self.B, device=dev), ne, output_size=n_rows)
             row_nnz = nip[1:] - nip[:-1]
             nnz = int(nip[-1])
             nnz_ent = torch.repeat_interleave(row_ent, row_nnz, output_size=nnz)
@@ -199,6 +237,8 @@ class EntityTronBatch:
             if self.quad:
                 self.nip, self.lcol, self.val = pad_rows_to_quads(self.nip, self.lcol, self.val)
                 nip = self.nip
+            ent_nnz = nip[self.row_ptr[1:]] - nip[self.row_ptr[:-1]]
+            res_sel = None if shifted else self._resident_mask(ne, de, ent_nnz, row_ent, row_nnz, stream_sel)
         self.rows, self.cols = row_sel, col_sel
         if shifted:
             # c in the batch's own packed column layout, the intercept's entity-local column per batch entity
@@ -207,7 +247,6 @@ class EntityTronBatch:
             if bool(((i0 < 0) | (i0 >= de)).any()):
                 raise ValueError("shifted fused TRON: an entity has no intercept column inside its coefficient range")
             self.shift = (c_all[col_sel].to(torch.float64).contiguous(), i0.to(torch.int32).contiguous())
-        row_ent = torch.repeat_interleave(torch.arange(self.B, device=dev), ne, output_size=n_rows)
         self.y, self.w = seg.y[row_sel].contiguous(), seg.w[row_sel].contiguous()
         self.n_rows = n_rows
         self.nnz = nnz
@@ -217,29 +256,26 @@ class EntityTronBatch:
         self.xf2 = None
         if LAZY_G0 and dev.type == "cuda":
             ent_len = self.nip[self.row_ptr[1:]] - self.nip[self.row_ptr[:-1]]
-            self.xf2 = torch.segment_reduce(self.val * self.val, "sum", lengths=ent_len).contiguous()
-        # launch classes by LDS size; inside a class the largest entities first (they bound the launch's tail).
-        # Entities of at most HESS_DMAX coefficients (tall: the row space took the wide ones) run the exact-Hessian
-        # kernel (MFMA), the others the sparse Hessian-vector kernel.
-        ent_nnz = (nip[self.row_ptr[1:]] - nip[self.row_ptr[:-1]])
+            if self.val.numel():
+                self.xf2 = torch.segment_reduce(self.val * self.val, "sum", lengths=ent_len).contiguous()
+            else:                                      # every row went to the narrow stream
+                self.xf2 = torch.zeros(self.B, dtype=torch.float64, device=dev)
+            if self.narrow is not None:
+                # fp64 sums over the widened values (a temporary); an entity has entries in one stream only
+                from ..ops.native import narrow_quad_parts
+                prec, n_nip, n_cols, n_rec = self.narrow
+                nv = narrow_quad_parts(prec, n_cols, n_rec)[1]
+                n_len = n_nip[self.row_ptr[1:]] - n_nip[self.row_ptr[:-1]]
+                self.xf2 = (self.xf2 + torch.segment_reduce(nv * nv, "sum", lengths=n_len)).contiguous()
+                del nv
+        # launch classes by LDS size; inside a class the largest entities first (they bound the launch's tail)
         if nnz and int(ent_nnz.max()) >= (1 << 31):
             raise ValueError("an entity of the fused batch has >= 2^31 non-zeros (32-bit kernel offsets)")
         self.launches = []
-        hess = (de <= HESS_DMAX) & (not shifted)
         # register-resident tasks (one persistent launch): clusters (k > 1 workgroups) first, largest first
         self.res = None
-        stream_sel = ~hess
-        if RESIDENT != "0" and bool(stream_sel.any()) and not shifted:
-            from ..ops.native import re_res_params
-            cap, rdmax, grid = re_res_params()
-            kmax = min(RES_KMAX, grid // 2)
-            ent_maxrow = torch.zeros(self.B, dtype=torch.int64, device=dev).scatter_reduce_(
-                0, row_ent, row_nnz, reduce="amax", include_self=True)
-            k_e = (ne + cap - 1) // cap
-            res = stream_sel & (de <= rdmax) & (ent_maxrow <= RES_ROW_NNZ) & (k_e <= kmax)
-            if RESIDENT != "force":
-                # tail entities only: one workgroup streaming such an entity would outlast the whole launch
-                res &= ent_nnz * RES_TAIL_SHARE > int(ent_nnz[stream_sel].sum())
+        if res_sel is not None:
+            res, k_e, grid = res_sel
             if bool(res.any()):
                 idx = torch.nonzero(res).squeeze(1)
                 # clusters first (descending k), then single-workgroup entities by descending non-zeros
@@ -266,11 +302,41 @@ class EntityTronBatch:
                 self.launches.append((dm if shifted else _launch_dmax(dm, de[idx], is_h),
                                       order.to(torch.int32).contiguous(), bool(is_h)))
 
+    def _resident_mask(self, ne, de, ent_nnz, row_ent, row_nnz, stream_sel):
+        """``(mask, k_e, grid)``: [B] bool, the entities of ``stream_sel`` that go to the register-resident launch,
+        the workgroups each entity would take there and the launch's grid (None: the policy is off or nothing to
+        choose from). ``ent_nnz``: slots per entity as gathered; ``row_nnz``: entries per batch row."""
+        if RESIDENT == "0" or not bool(stream_sel.any()):
+            return None
+        from ..ops.native import re_res_params
+        cap, rdmax, grid = re_res_params()
+        kmax = min(RES_KMAX, grid // 2)
+        ent_maxrow = torch.zeros(self.B, dtype=torch.int64, device=ne.device).scatter_reduce_(
+            0, row_ent, row_nnz, reduce="amax", include_self=True)
+        k_e = (ne + cap - 1) // cap
+        res = stream_sel & (de <= rdmax) & (ent_maxrow <= RES_ROW_NNZ) & (k_e <= kmax)
+        if RESIDENT != "force":
+            # tail entities only: one workgroup streaming such an entity would outlast the whole launch
+            res &= ent_nnz * RES_TAIL_SHARE > int(ent_nnz[stream_sel].sum())
+        return res, k_e, grid
+
+    def stream_bytes(self) -> dict:
+        """Bytes of the gathered row copies: the fp64 stream (2 B column + 8 B value per slot), the narrow quad
+        stream (f32: 2 + 4 B, bf16: 2 + 2 B per slot) and the slots of each (padding included)."""
+        wide = int(self.val.numel())
+        out = {"f64_slots": wide, "f64_bytes": 10 * wide, "narrow_slots": 0, "narrow_bytes": 0}
+        if self.narrow is not None:
+            prec, _, n_cols, n_rec = self.narrow
+            out["narrow_slots"] = int(n_rec.numel())
+            out["narrow_bytes"] = int(n_rec.numel() * n_rec.element_size()
+                                      + (0 if n_cols is None else n_cols.numel() * n_cols.element_size()))
+        return out
+
     def solve(self, loss, l2: float, W0: Optional[torch.Tensor], offsets: torch.Tensor, tol: float, max_iter: int,
               max_fail: int = 5, max_cg: int = 20) -> FusedResult:
         """Solve every entity of the batch from ``W0`` (packed over the batch's coefficients; None = the last
         solution, or zeros the first time). ``offsets``: per batch row."""
-        from ..ops.native import re_tron_csr
+        from ..ops.native import RE_LEAN_DMAX, re_tron_csr
         dev = self.y.device
         if self.res is not None and self.res["grid"] < self.res["kmax"]:
             # the members of a cluster meet at a barrier: with fewer workgroups than members they would wait for
@@ -302,7 +368,8 @@ class EntityTronBatch:
                 continue
             re_tron_csr(order, self.row_ptr, self.col_ptr, self.nip, self.lcol, self.val, self.y, off, self.w,
                         self.scr, W, f, iters, reason, z, loss.loss_id, l2, tol, max_iter, max_fail, max_cg, dm,
-                        hessian=is_h, gsc=self.gsc, quad=self.quad, xf2=self.xf2)
+                        hessian=is_h, gsc=self.gsc, quad=self.quad, xf2=self.xf2,
+                        narrow=self.narrow if not is_h and dm <= RE_LEAN_DMAX else None)
         self.W = W
         # the error flag stays on the device: reading it here would wait for the whole launch before the caller
         # can queue concurrent work (the row-space side stream); callers call FusedResult.check_error() later

@@ -9,6 +9,12 @@ labels. Times the whole batch, the largest entities alone, and the rest alone (t
 compares the two kernels' models.
 
 usage: python scripts/re_fused_bench.py [n_entities=43000] [kernels, e.g. stream,res]
+       python scripts/re_fused_bench.py [n_entities] --re-precision f64,f32,bf16 [--rounds 3]
+
+``--re-precision``: the lean kernel alone on values pre-rounded to bf16, once per listed storage setting (``f64``: the
+fp64 quad rows; ``f32`` / ``bf16``: the narrow quad stream of ``csr_gather_quads``), the settings alternating over
+``--rounds`` rounds: min / median launch time per setting, bytes of each stream, and whether models, margins and
+iteration counts are identical across the settings.
 """
 import os
 import sys
@@ -19,6 +25,17 @@ import torch
 
 from photon_ml_amd.ops.native import re_lib, re_res_params, re_tron_csr, re_tron_res
 
+def _option(name, default=None):
+    if name not in sys.argv:
+        return default
+    i = sys.argv.index(name)
+    value = sys.argv[i + 1]
+    del sys.argv[i:i + 2]
+    return value
+
+
+RE_PRECISION = _option("--re-precision")
+ROUNDS = int(_option("--rounds", "3"))
 E = int(sys.argv[1]) if len(sys.argv) > 1 else 43_000
 KERNELS = sys.argv[2].split(",") if len(sys.argv) > 2 else ["stream", "res"]
 dev = torch.device("cuda")
@@ -41,6 +58,8 @@ lcol = torch.cat([cols, torch.full((N, 1), d - 1, device=dev)], 1).reshape(-1).t
 del cols
 val = torch.randn(N * NNZ, generator=g, device=dev, dtype=torch.float64)
 val.view(N, NNZ)[:, -1] = 1.0
+if RE_PRECISION:
+    val = val.to(torch.float32).to(torch.bfloat16).to(torch.float64)
 DMAX = int(os.environ.get("PML_BENCH_DMAX", "1008"))     # lean launches: widest entity rounded up to 8
 QUAD = os.environ.get("PML_BENCH_QUAD", "1") != "0"     # lean kernel on rows padded to whole quads
 nip = torch.arange(N + 1, dtype=torch.int64, device=dev) * NNZ
@@ -73,7 +92,7 @@ def res_tasks(order):
     return ents.to(torch.int32).contiguous(), t0.to(torch.int32).contiguous(), ws, int((k > 1).sum())
 
 
-def run(kernel, order, reps=3):
+def run(kernel, order, reps=3, narrow=None):
     W = torch.zeros(E * d, dtype=torch.float64, device=dev)
     f = torch.empty(E, dtype=torch.float64, device=dev)
     it = torch.empty(E, dtype=torch.int32, device=dev)
@@ -91,7 +110,7 @@ def run(kernel, order, reps=3):
             q = kernel == "lean" and QUAD
             re_tron_csr(order, row_ptr, col_ptr, nip_q if q else nip, lcol_q if q else lcol, val_q if q else val, y,
                         off, wt, scr, W, f, it, rc, z, 0, 1.0, 1e-12, 10, 5, 20, DMAX if kernel == "lean" else 1024,
-                        npass=np_, lean=kernel == "lean", quad=q)
+                        npass=np_, lean=kernel == "lean", quad=q, narrow=narrow)
             return None
     err = call(npass)
     torch.cuda.synchronize()
@@ -107,6 +126,36 @@ def run(kernel, order, reps=3):
     gb = float((npass[sel].double() * (n_e[sel] * (NNZ * 10 + 16)).double()).sum()) / 1e9
     return ms, it.clone(), gb, float(npass[sel].double().mean()), W.clone(), z.clone()
 
+
+if RE_PRECISION:
+    from photon_ml_amd.ops.native import csr_gather_quads
+    assert QUAD, "the storage settings compare quad rows"
+    settings = RE_PRECISION.split(",")
+    streams, nbytes = {}, {}
+    for p in settings:
+        if p == "f64":
+            streams[p], nbytes[p] = None, 10 * val_q.numel()
+        else:
+            c_, r_ = csr_gather_quads(nip, lcol.to(torch.int64), val, torch.arange(N, device=dev), nip_q,
+                                      torch.zeros(N, dtype=torch.int64, device=dev), p)
+            streams[p] = (p, nip_q, c_, r_)
+            nbytes[p] = r_.numel() * r_.element_size() + (0 if c_ is None else 2 * c_.numel())
+    times, out = {p: [] for p in settings}, {}
+    for _ in range(ROUNDS):
+        for p in settings:
+            ms, it, _, mp, W, z = run("lean", order_all, reps=10, narrow=streams[p])
+            times[p].append(ms)
+            out[p] = (W, z, it, mp)
+    base = out[settings[0]]
+    for p in settings:
+        t = sorted(times[p])
+        W, z, it, mp = out[p]
+        same = bool(torch.equal(W, base[0]) and torch.equal(z, base[1]) and torch.equal(it, base[2]))
+        print(f"lean {p}: min {t[0]:.2f} ms, median {t[len(t) // 2]:.2f} ms over {ROUNDS} rounds "
+              f"({', '.join(f'{v:.2f}' for v in times[p])}); rows {nbytes[p] / 2**20:.0f} MiB "
+              f"({nbytes[p] / val_q.numel():.0f} B per slot); mean passes/entity {mp:.1f}, mean TRON iterations "
+              f"{it.double().mean():.3f}; W / margins / iterations identical to {settings[0]}: {same}", flush=True)
+    sys.exit(0)
 
 models = {}
 for kern in KERNELS:
