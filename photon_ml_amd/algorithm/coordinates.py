@@ -272,6 +272,9 @@ class FixedEffectCoordinate(Coordinate):
 _RS_WARM = object()   # warm-start marker: the last segmented solve kept only row-space coordinates
 
 
+SHIFT_ROUTES = ("csr", "auto")      # RandomEffectCoordinate(shift_routes=): fused routes under normalization shifts
+
+
 class RandomEffectCoordinate(Coordinate):
     """Per-entity GLMs solved in size buckets on the device (K7).
 
@@ -285,13 +288,17 @@ class RandomEffectCoordinate(Coordinate):
     def __init__(self, coordinate_id: str, data: GameData, data_config: RandomEffectDataConfiguration,
                  opt_config: GLMOptimizationConfiguration, task, compute_variance: bool = False, device=None,
                  dtype=torch.float64, entity_subset=None, layout: str = "auto",
-                 prior: Optional[RandomEffectModel] = None, normalization: Optional[NormalizationContext] = None):
+                 prior: Optional[RandomEffectModel] = None, normalization: Optional[NormalizationContext] = None,
+                 shift_routes: str = "csr"):
         """``normalization``: the ``NormalizationContext`` of the coordinate's feature shard (None or an identity
         context: none). The dataset folds it into the data once (``NormFold``): inside this coordinate every solver
         state is the transformed-space ``w'`` (each entity's problem is solved over ``X' = (X - s) f``, the penalty is
         on ``w'``), outside it everything stays in the original space. Scale-only contexts run every solver route on
         the scaled data; a context with shifts runs the shifted fused TRON (``re_tron_csr_kernel<LOSS, true>``) or
-        the pass path.
+        the pass path. ``shift_routes`` chooses the fused routes under shifts: ``"csr"`` (default) that one kernel for
+        every entity of at most 2048 coefficients; ``"auto"`` also the row-space route for wide entities (``K' = X'
+        X'^T`` from ``seg_gram_kernel<S, STAGE, true>``, back-map ``rs_primal_kernel<PT, true>``) and
+        ``re_tron_tall_kernel<T, LOSS, true>`` for entities of at most 64 coefficients. It has no effect without shifts.
 
         ``prior``: yesterday's model of this coordinate as a Gaussian prior (incremental training): the penalty
         becomes ``lambda/2 sum_j (w_j - mu_j)^2 / sigma_j^2`` per entity and feature (``mu = 0, sigma^2 = 1`` where
@@ -299,6 +306,10 @@ class RandomEffectCoordinate(Coordinate):
         coordinate every solver state is ``v = (w - mu) / sigma`` under plain L2, outside it (models, scores,
         warm starts) everything stays in the original space."""
         self.coordinate_id = coordinate_id
+        if shift_routes not in SHIFT_ROUTES:
+            raise ValueError(f"coordinate {coordinate_id}: shift_routes must be one of {SHIFT_ROUTES}, got "
+                             f"{shift_routes!r}")
+        self.shift_routes = shift_routes
         self.data = data
         self.data_config = data_config
         self.task = TaskType.parse(task)
@@ -376,6 +387,11 @@ class RandomEffectCoordinate(Coordinate):
     def _shifted(self) -> bool:
         nf = self._norm
         return nf is not None and nf.has_shift
+
+    @property
+    def _shift_auto(self) -> bool:
+        """Shifted data with the row-space and tall routes enabled (``shift_routes="auto"``)."""
+        return self._shifted and self.shift_routes == "auto"
 
     def _check_normalization_config(self, data_config):
         """What normalization of a random effect cannot be combined with (ValueError naming the coordinate, before
@@ -781,12 +797,14 @@ class RandomEffectCoordinate(Coordinate):
             rs = None
             if kind == "tron":
                 with Timed(f"RE {self.coordinate_id}: row-space batch", log, logging.DEBUG):
-                    rs = self._row_space(l1, oc)
+                    rs = self._row_space(l1, oc, components=True)
                     rs = rs if rs is not None and rs.B else None
             n_e = seg.row_ptr[1:] - seg.row_ptr[:-1]
             done = rs.mask.clone() if rs is not None else torch.zeros(seg.B, dtype=torch.bool, device=seg.y.device)
             with Timed(f"RE {self.coordinate_id}: fused primal batch", log, logging.DEBUG):
-                fused = (EntityTronBatch if kind == "tron" else EntityLbfgsBatch)(ds, (~done) & (n_e > 0))
+                todo = (~done) & (n_e > 0)
+                fused = (EntityTronBatch(ds, todo, shift_tall=self._shift_auto) if kind == "tron" else
+                         EntityLbfgsBatch(ds, todo))
             if fused.B:
                 done |= fused.mask
             else:
@@ -830,10 +848,17 @@ class RandomEffectCoordinate(Coordinate):
         out = {"row_space": 0 if rs is None else int(rs.B), "fused": 0 if fused is None else int(fused.B),
                "pass_path": 0 if sub is None else int(sub.entities.numel())}
         if self._shifted:
-            # every fused entity on re_tron_csr_kernel<LOSS, true>; no row-space, lean, tall, Hessian or resident launch
             out["shifted"] = True
-            out["fused_kernel"] = "re_tron_csr_kernel<LOSS, true>"
             out["lean"] = out["hessian"] = 0
+            if self._shift_auto:
+                # the fused batch's tall launches (re_tron_tall_kernel<T, LOSS, true>), counted among "fused" too; the
+                # rest of it on re_tron_csr_kernel<LOSS, true>; still no lean or resident launch
+                if fused is not None:
+                    out["hessian"] = sum(int(order.numel()) for _, order, is_h in fused.launches if is_h)
+            else:
+                # every fused entity on re_tron_csr_kernel<LOSS, true>; no row-space, lean, tall, Hessian or resident
+                # launch
+                out["fused_kernel"] = "re_tron_csr_kernel<LOSS, true>"
         if fused is not None:
             out["fused_launches"] = len(fused.launches)
             out["heavy_to_pass_path"] = int(fused.n_heavy)
@@ -1062,15 +1087,20 @@ class RandomEffectCoordinate(Coordinate):
         self._sub = (frozen, sub)
         return sub
 
-    def _row_space(self, l1: float, oc):
-        """Row-space batch for the wide entities (built once per dataset), or None when not applicable."""
+    def _row_space(self, l1: float, oc, components: bool = False):
+        """Row-space batch for the wide entities (built once per dataset), or None when not applicable. Under shifts
+        only with ``shift_routes="auto"`` and for the component solve (``components``): the batch then carries the
+        shift itself (``RowSpaceBatch(..., shift=)``), and takes only what its two shifted kernels reach."""
         from ..optimization.row_space import RowSpaceBatch, row_space_eligible
+        seg = self.dataset.seg
+        with_shift = self._shift_auto and components and seg.y.device.type == "cuda"
         if (os.environ.get("PML_RE_ROW_SPACE", "1") == "0"
-                or not row_space_eligible(l1, oc.constraint_map, shift=self._shifted)):
+                or not row_space_eligible(l1, oc.constraint_map, shift=self._shifted and not with_shift)):
             return None
         if getattr(self, "_rs", None) is None:
-            self._rs = RowSpaceBatch(self.dataset.seg, nmax=int(os.environ.get("PML_RS_NMAX", "128")),
-                                     csr=getattr(self.dataset, "_seg_csr", None))
+            self._rs = RowSpaceBatch(seg, nmax=int(os.environ.get("PML_RS_NMAX", "128")),
+                                     csr=getattr(self.dataset, "_seg_csr", None),
+                                     shift=seg.shift if with_shift else None)
         return self._rs
 
     def _warm_start_segmented(self, model):

@@ -152,6 +152,10 @@ def build_parser() -> argparse.ArgumentParser:
                    help="apply --normalization to the random-effect coordinates too (one context per feature shard "
                         "from the statistics of all rows; each entity is solved in the normalized space); default: "
                         "random-effect coordinates ignore normalization")
+    p.add_argument("--random-effect-shift-routes", default="csr",
+                   help="fused solver routes of normalized random-effect coordinates under a type with shifts "
+                        "(STANDARDIZATION): csr = one streaming kernel for every entity (default), auto = also the "
+                        "row-space route for wide entities and the tall-narrow kernel")
     p.add_argument("--data-summary-directory")
     p.add_argument("--tree-aggregate-depth", type=int, default=1,
                    help="reduction depth of the reference's treeAggregate: >= 2 selects RCCL's tree all-reduce "
@@ -284,6 +288,9 @@ class GameTrainingDriver(GameDriverBase):
             raise ValueError("hyper-parameter tuning needs --hyper-parameter-tuning-iterations > 0")
         if self.args.coordinate_descent_iterations <= 0:
             raise ValueError("coordinate descent iterations must be > 0")
+        if self.args.random_effect_shift_routes not in ("csr", "auto"):
+            raise ValueError(f"--random-effect-shift-routes must be csr or auto, got "
+                             f"{self.args.random_effect_shift_routes!r}")
 
     def id_tags(self):
         return sorted({t for cc in self.coord_configs.values() for t in cc.id_tag_names})
@@ -359,7 +366,8 @@ class GameTrainingDriver(GameDriverBase):
                .set_tree_aggregate_depth(a.tree_aggregate_depth)
                .set_normalization(self.normalization, {sid: m.intercept_index for sid, m in maps.items()},
                                   collect_statistics=bool(a.data_summary_directory))
-               .set_random_effect_normalization(a.normalize_random_effects))
+               .set_random_effect_normalization(a.normalize_random_effects,
+                                                shift_routes=a.random_effect_shift_routes))
         est.coordinates_built_callback = coordinates_built
         if a.model_input_directory:
             from ..io.model_io import load_game_model

@@ -65,6 +65,7 @@ class GameEstimator:
         self.intercept_indices_by_shard: Dict[str, Optional[int]] = {}
         self.collect_statistics = False
         self.normalize_random_effects = False                     # see set_random_effect_normalization
+        self.random_effect_shift_routes = "csr"
         self.feature_statistics: Dict[str, BasicStatisticalSummary] = {}   # by feature shard id, filled by fit
         self.coordinates_built_callback = None
         self.variance_computation_type = VarianceComputationType.NONE   # compute_variance: its boolean view
@@ -120,7 +121,7 @@ class GameEstimator:
         self.collect_statistics = bool(collect_statistics)
         return self
 
-    def set_random_effect_normalization(self, b: bool):
+    def set_random_effect_normalization(self, b: bool, shift_routes: str = "csr"):
         """Normalization for random-effect coordinates too (default False: they ignore it). When on, every
         random-effect coordinate gets a context: the explicit one of :meth:`set_coordinate_normalization_contexts`
         if its id is there, otherwise one built by TYPE (:meth:`set_normalization`) from the statistics of its whole
@@ -128,8 +129,14 @@ class GameEstimator:
         then solved in the normalized space (penalties on the transformed coefficients) and the model comes back in
         the original space. Not combinable with a prior model on the same coordinate, the RANDOM projector or a
         process group; a type with shifts (STANDARDIZATION) needs an intercept among every trained entity's features
-        and supports no coefficient variances (ValueError naming the coordinate, before any training)."""
+        and supports no coefficient variances (ValueError naming the coordinate, before any training).
+        ``shift_routes``: the fused solver routes under a type with shifts, ``"csr"`` (default) or ``"auto"``
+        (``RandomEffectCoordinate(shift_routes=)``); anything else is a ValueError here."""
+        from ..algorithm.coordinates import SHIFT_ROUTES
+        if shift_routes not in SHIFT_ROUTES:
+            raise ValueError(f"shift_routes must be one of {SHIFT_ROUTES}, got {shift_routes!r}")
         self.normalize_random_effects = bool(b)
+        self.random_effect_shift_routes = shift_routes
         return self
 
     def _random_effect_context(self, data: GameData, cid: str, shard_id: str) -> Optional[NormalizationContext]:
@@ -279,9 +286,10 @@ class GameEstimator:
                                                             prior=self._prior_for(cid, False))
             elif isinstance(dc, RandomEffectDataConfiguration):
                 cls = ShardedRandomEffectCoordinate if is_dist() else RandomEffectCoordinate
+                kw = {} if is_dist() else {"shift_routes": self.random_effect_shift_routes}
                 coords[cid] = cls(cid, data, dc, oc, self.training_task, self.variance_computation_type, self.device,
                                   prior=self._prior_for(cid, True),
-                                  normalization=self._random_effect_context(data, cid, dc.feature_shard_id))
+                                  normalization=self._random_effect_context(data, cid, dc.feature_shard_id), **kw)
             else:
                 explicit = self.coordinate_normalization_contexts.get(cid)
                 prior = self._prior_for(cid, False)

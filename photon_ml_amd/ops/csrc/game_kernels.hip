@@ -316,13 +316,28 @@ __global__ __launch_bounds__(256) void tl_compact_kernel(CmpArgs a) {
 // coalesced whole-wave loads; the per-lane walks over row j then read LDS instead of issuing one uncoalesced global
 // load per entry (64 lanes on 64 different rows) -- the dependent chain of a walk is LDS-latency bound, not
 // HBM-latency bound. Same fma sequence, bitwise equal to the unstaged walk.
-template <int S, bool STAGE>
+// SHIFT: the entity's design matrix is X' = X (I - e_ic c^T), x'_r = x_r - x_{r,ic} c (the shift of a STANDARDIZATION
+// context; ic = the entity's intercept column, c_ic = 0) and the kernel writes K' = X' X'^T directly: the rank-2
+// fix-up K - x0 m^T - m x0^T + |c|^2 x0 x0^T would subtract numbers of the size of K from each other. Chosen design:
+// * c_e is copied once into LDS behind the image, and x0[j] = x_{j,ic} of every row is found by one walk of lane j
+//   over its own row before the first round;
+// * a round scatters its S rows as above, then one DENSE sweep (lane l: columns l, l + 64, ...) turns slot s into
+//   the shifted row, img[c S + s] = x_ic - x0[i] c_c, and in the same sweep sums q_s = c . x'_i: per-lane partial
+//   sums in column order, then a fixed-order wave butterfly (every lane holds the same bits);
+// * lane j walks its own SPARSE row as above and finishes with K'_ji = sum_t v_jt img_i[col_t] - x0[j] q_i
+//   (= (x_j - x0[j] c) . x'_i): the walks stay sparse, only the image is dense;
+// * the image is cleared densely after the round (the shifted row has no zero pattern).
+// One wave per entity and S by LDS size as without a shift (the launcher counts the extra d_e + n doubles); no
+// atomics, every sum in a fixed order: bitwise repeatable. SHIFT = false compiles to the code above unchanged.
+template <int S, bool STAGE, bool SHIFT = false>
 __global__ __launch_bounds__(64) void seg_gram_kernel(int B, int n, int dmax, const long long* __restrict__ ents,
                                                       const long long* __restrict__ row_ptr,
                                                       const long long* __restrict__ col_ptr,
                                                       const long long* __restrict__ nip,
                                                       const long long* __restrict__ pos,
-                                                      const double* __restrict__ val, double* __restrict__ K) {
+                                                      const double* __restrict__ val, double* __restrict__ K,
+                                                      const double* __restrict__ shc = nullptr,
+                                                      const long long* __restrict__ shi0 = nullptr) {
   extern __shared__ double img[];
   const int lane = threadIdx.x;
   const long long b = blockIdx.x;
@@ -334,8 +349,11 @@ __global__ __launch_bounds__(64) void seg_gram_kernel(int B, int n, int dmax, co
   const int de = (int)(col_ptr[e + 1] - cb);
   const long long e0 = nip[r0];
   const int enz = (int)(nip[r0 + ne] - e0);
-  // staged layout after the image: values [enz] doubles, local columns [enz] uint16, row offsets [ne + 1] int
-  double* sval = img + (size_t)dmax * S;
+  // SHIFT, after the image: c_e [dmax] and the rows' intercept values x0 [n]
+  double* cs = img + (size_t)dmax * S;
+  double* x0 = cs + (SHIFT ? dmax : 0);
+  // staged layout after that: values [enz] doubles, local columns [enz] uint16, row offsets [ne + 1] int
+  double* sval = x0 + (SHIFT ? n : 0);
   unsigned short* scol = (unsigned short*)(sval + enz);
   int* sptr = (int*)(scol + ((enz + 3) & ~3));
   for (int c = lane; c < de * S; c += 64) img[c] = 0.0;
@@ -346,7 +364,26 @@ __global__ __launch_bounds__(64) void seg_gram_kernel(int B, int n, int dmax, co
     }
     for (int i = lane; i <= ne; i += 64) sptr[i] = (int)(nip[r0 + i] - e0);
   }
+  if constexpr (SHIFT)
+    for (int c = lane; c < de; c += 64) cs[c] = shc[cb + c];
   __syncthreads();
+  if constexpr (SHIFT) {
+    const long long ic = shi0[e];                 // compared only, never an index
+    for (int j = lane; j < n; j += 64) {
+      double v0 = 0.0;
+      if (j < ne) {
+        if (STAGE) {
+          for (int t = sptr[j]; t < sptr[j + 1]; ++t)
+            if ((long long)scol[t] == ic) v0 = sval[t];
+        } else {
+          for (long long t = nip[r0 + j]; t < nip[r0 + j + 1]; ++t)
+            if (pos[t] - cb == ic) v0 = val[t];
+        }
+      }
+      x0[j] = v0;
+    }
+    __syncthreads();
+  }
   double* Kb = K + b * (long long)n * n;
   for (int i0 = 0; i0 < ne; i0 += S) {
     const int ns = ne - i0 < S ? ne - i0 : S;
@@ -360,6 +397,28 @@ __global__ __launch_bounds__(64) void seg_gram_kernel(int B, int n, int dmax, co
       }
     }
     __syncthreads();
+    double q[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) q[s] = 0.0;
+    if constexpr (SHIFT) {
+      double xs[S];
+#pragma unroll
+      for (int s = 0; s < S; ++s) xs[s] = s < ns ? x0[i0 + s] : 0.0;
+      for (int c = lane; c < de; c += 64) {
+        const double cc = cs[c];
+        double* im = img + c * S;
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+          const double v = fma(-xs[s], cc, im[s]);
+          im[s] = v;
+          q[s] = fma(cc, v, q[s]);
+        }
+      }
+#pragma unroll
+      for (int s = 0; s < S; ++s)
+        for (int o = 32; o > 0; o >>= 1) q[s] += __shfl_xor(q[s], o, 64);
+      __syncthreads();
+    }
     // lane takes rows j = lane, lane + 64, lane + 128 (n <= 192)
     for (int j = lane; j < n; j += 64) {
       double acc[S];
@@ -383,19 +442,28 @@ __global__ __launch_bounds__(64) void seg_gram_kernel(int B, int n, int dmax, co
             for (int s = 0; s < S; ++s) acc[s] = fma(v, im[s], acc[s]);
           }
         }
+        if constexpr (SHIFT) {
+          const double xj = x0[j];
+#pragma unroll
+          for (int s = 0; s < S; ++s) acc[s] = fma(-xj, q[s], acc[s]);
+        }
       }
 #pragma unroll
       for (int s = 0; s < S; ++s)
         if (s < ns) Kb[(long long)j * n + i0 + s] = acc[s];
     }
     __syncthreads();
-    for (int s = 0; s < ns; ++s) {
-      if (STAGE) {
-        const int ib = sptr[i0 + s], ie = sptr[i0 + s + 1];
-        for (int t = ib + lane; t < ie; t += 64) img[(int)scol[t] * S + s] = 0.0;
-      } else {
-        const long long ib = nip[r0 + i0 + s], ie = nip[r0 + i0 + s + 1];
-        for (long long t = ib + lane; t < ie; t += 64) img[(pos[t] - cb) * S + s] = 0.0;
+    if constexpr (SHIFT) {
+      for (int c = lane; c < de * S; c += 64) img[c] = 0.0;
+    } else {
+      for (int s = 0; s < ns; ++s) {
+        if (STAGE) {
+          const int ib = sptr[i0 + s], ie = sptr[i0 + s + 1];
+          for (int t = ib + lane; t < ie; t += 64) img[(int)scol[t] * S + s] = 0.0;
+        } else {
+          const long long ib = nip[r0 + i0 + s], ie = nip[r0 + i0 + s + 1];
+          for (long long t = ib + lane; t < ie; t += 64) img[(pos[t] - cb) * S + s] = 0.0;
+        }
       }
     }
     __syncthreads();
@@ -451,14 +519,20 @@ __global__ __launch_bounds__(64) void batched_chol_kernel(int B, int n, const lo
 // handled entities' rows (the shard-wide transpose pass read every entity's).
 // PT: int64 or int32 packed positions (int32 when the packed vector has < 2^31 coefficients: 4 bytes less per entry
 // of a bandwidth-bound pass)
-template <typename PT>
+// SHIFT: the back-map of X' = X (I - e_ic c^T): w'_j = (X^T r)_j - c_j (x0 . r). x0 . r needs no sum of its own: the
+// wave accumulates it through the intercept's slot, so acc[ic] after the rows IS x0 . r; every lane reads it (one
+// broadcast LDS read) and corrects its own slots on their way to global memory. Slot ic itself is stored as it is
+// (c_ic = 0), so no LDS slot is rewritten. ``shc`` is packed like W, ``shi0`` per entity of row_ptr / col_ptr.
+template <typename PT, bool SHIFT = false>
 __global__ __launch_bounds__(64) void rs_primal_kernel(const long long* __restrict__ ents,
                                                        const long long* __restrict__ row_ptr,
                                                        const long long* __restrict__ col_ptr,
                                                        const long long* __restrict__ nip,
                                                        const PT* __restrict__ pos,
                                                        const double* __restrict__ val, const double* __restrict__ r,
-                                                       double* __restrict__ W) {
+                                                       double* __restrict__ W,
+                                                       const double* __restrict__ shc = nullptr,
+                                                       const long long* __restrict__ shi0 = nullptr) {
   extern __shared__ double acc[];
   const int lane = threadIdx.x;
   const long long e = ents[blockIdx.x];
@@ -479,7 +553,13 @@ __global__ __launch_bounds__(64) void rs_primal_kernel(const long long* __restri
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
   }
-  for (int j = lane; j < d; j += 64) W[c0 + j] = acc[j];
+  if constexpr (SHIFT) {
+    const long long ic = shi0[e];
+    const double a0 = (ic >= 0 && ic < d) ? acc[ic] : 0.0;
+    for (int j = lane; j < d; j += 64) W[c0 + j] = j == ic ? acc[j] : fma(-shc[c0 + j], a0, acc[j]);
+  } else {
+    for (int j = lane; j < d; j += 64) W[c0 + j] = acc[j];
+  }
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2129,36 +2209,60 @@ void pml_seg_gram_set_s(int s) { g_seg_gram_s = (s == 1 || s == 2 || s == 4 || s
 
 // K [B, n, n] for the entities ents[B]; dmax = max projected columns of those entities (LDS image size); maxnnz = max
 // non-zeros of one of those entities (> 0: stage the entries in LDS when they fit, see seg_gram_kernel STAGE).
-int pml_seg_gram(int B, int n, int dmax, long long maxnnz, const long long* ents, const long long* row_ptr,
-                 const long long* col_ptr, const long long* nip, const long long* pos, const double* val, double* K,
-                 void* stream) {
+// shc / shi0 (both or neither): the shift c per packed column and the intercept's local column per entity of
+// row_ptr / col_ptr (0 <= i0 < d_e, c[i0] = 0) -- seg_gram_kernel<S, STAGE, true> writes K' = X' X'^T.
+static int seg_gram_launch(int B, int n, int dmax, long long maxnnz, const long long* ents, const long long* row_ptr,
+                           const long long* col_ptr, const long long* nip, const long long* pos, const double* val,
+                           double* K, const double* shc, const long long* shi0, void* stream) {
   if (B <= 0) return 0;
   if (n < 1 || n > 192 || dmax < 0 || (size_t)dmax * sizeof(double) > 160 * 1024) return -22;
-  // rows per scatter round: as many as keep the image <= 32 KB (>= 5 one-wave workgroups per CU)
+  const bool shift = shc != nullptr;
+  if (shift != (shi0 != nullptr)) return -22;
+  // rows per scatter round: as many as keep the image (with a shift: and c_e, x0) <= 32 KB (>= 5 one-wave workgroups
+  // per CU)
   const size_t d8 = (size_t)std::max(dmax, 1) * sizeof(double);
-  const int S = g_seg_gram_s > 0 ? g_seg_gram_s : (d8 * 8 <= 32768 ? 8 : d8 * 4 <= 32768 ? 4 : d8 * 2 <= 32768 ? 2 : 1);
-  const size_t img = d8 * (size_t)S;
+  const size_t extra = shift ? d8 + (size_t)n * sizeof(double) : 0;
+  const int S = g_seg_gram_s > 0 ? g_seg_gram_s
+                                 : (d8 * 8 + extra <= 32768 ? 8 : d8 * 4 + extra <= 32768 ? 4
+                                    : d8 * 2 + extra <= 32768 ? 2 : 1);
+  const size_t img = d8 * (size_t)S + extra;
   const size_t stage = maxnnz > 0 ? (size_t)maxnnz * 10 + 8 + (size_t)(n + 1) * 4 + 16 : 0;
   const bool staged = maxnnz > 0 && img + stage <= 64 * 1024;
   const size_t lds = staged ? img + stage : img;
   if (lds > 160 * 1024) return -22;
   hipStream_t st = (hipStream_t)stream;
+#define SEG_GRAM_LAUNCH_K(SS, ST, SH)                                                                            \
+  hipLaunchKernelGGL((seg_gram_kernel<SS, ST, SH>), dim3((unsigned)B), dim3(64), lds, st, B, n, std::max(dmax, 1), \
+                     ents, row_ptr, col_ptr, nip, pos, val, K, shc, shi0)
 #define SEG_GRAM_LAUNCH(SS)                                                                                       \
   do {                                                                                                           \
-    if (staged)                                                                                                  \
-      hipLaunchKernelGGL((seg_gram_kernel<SS, true>), dim3((unsigned)B), dim3(64), lds, st, B, n, std::max(dmax, 1), \
-                         ents, row_ptr, col_ptr, nip, pos, val, K);                                              \
-    else                                                                                                         \
-      hipLaunchKernelGGL((seg_gram_kernel<SS, false>), dim3((unsigned)B), dim3(64), lds, st, B, n, std::max(dmax, 1), \
-                         ents, row_ptr, col_ptr, nip, pos, val, K);                                              \
+    if (shift) {                                                                                                 \
+      if (staged) SEG_GRAM_LAUNCH_K(SS, true, true);                                                             \
+      else SEG_GRAM_LAUNCH_K(SS, false, true);                                                                   \
+    } else if (staged) SEG_GRAM_LAUNCH_K(SS, true, false);                                                       \
+    else SEG_GRAM_LAUNCH_K(SS, false, false);                                                                    \
   } while (0)
   if (S == 8) SEG_GRAM_LAUNCH(8);
   else if (S == 4) SEG_GRAM_LAUNCH(4);
   else if (S == 2) SEG_GRAM_LAUNCH(2);
   else SEG_GRAM_LAUNCH(1);
 #undef SEG_GRAM_LAUNCH
+#undef SEG_GRAM_LAUNCH_K
   LAUNCH_CHECK();
   return 0;
+}
+
+int pml_seg_gram(int B, int n, int dmax, long long maxnnz, const long long* ents, const long long* row_ptr,
+                 const long long* col_ptr, const long long* nip, const long long* pos, const double* val, double* K,
+                 void* stream) {
+  return seg_gram_launch(B, n, dmax, maxnnz, ents, row_ptr, col_ptr, nip, pos, val, K, nullptr, nullptr, stream);
+}
+
+int pml_seg_gram_shift(int B, int n, int dmax, long long maxnnz, const long long* ents, const long long* row_ptr,
+                       const long long* col_ptr, const long long* nip, const long long* pos, const double* val,
+                       double* K, const double* shc, const long long* shi0, void* stream) {
+  if (shc == nullptr || shi0 == nullptr) return -22;
+  return seg_gram_launch(B, n, dmax, maxnnz, ents, row_ptr, col_ptr, nip, pos, val, K, shc, shi0, stream);
 }
 
 // In-place Cholesky of K [B, n, n] (n <= 192); nv[b] = valid rows of problem b (the rest: identity); info[B].
@@ -2174,20 +2278,44 @@ int pml_batched_chol(int B, int n, const long long* nv, double* K, int* info, vo
 // W (packed projected coefficients) of the entities ents[B] = X_e^T r over their rows; dmax = max projected columns
 // of those entities (LDS per wave). Other entities' coefficients are left untouched.
 // pos32: positions are int32 (else int64).
+// shc / shi0 (both or neither): rs_primal_kernel<PT, true>, the back-map of X' (shc packed like W, shi0 per entity of
+// row_ptr / col_ptr).
+static int rs_primal_launch(int B, int dmax, const long long* ents, const long long* row_ptr, const long long* col_ptr,
+                            const long long* nip, const void* pos, const double* val, const double* r, double* W,
+                            const double* shc, const long long* shi0, void* stream, int pos32) {
+  if (B <= 0) return 0;
+  if (dmax < 0 || (size_t)dmax * sizeof(double) > 64 * 1024) return -22;
+  const bool shift = shc != nullptr;
+  if (shift != (shi0 != nullptr)) return -22;
+  const size_t lds = (size_t)std::max(dmax, 1) * sizeof(double);
+  const dim3 g((unsigned)B), blk(64);
+  hipStream_t st = (hipStream_t)stream;
+  if (pos32) {
+    if (shift) hipLaunchKernelGGL((rs_primal_kernel<int, true>), g, blk, lds, st, ents, row_ptr, col_ptr, nip,
+                                  (const int*)pos, val, r, W, shc, shi0);
+    else hipLaunchKernelGGL((rs_primal_kernel<int, false>), g, blk, lds, st, ents, row_ptr, col_ptr, nip,
+                            (const int*)pos, val, r, W, shc, shi0);
+  } else {
+    if (shift) hipLaunchKernelGGL((rs_primal_kernel<long long, true>), g, blk, lds, st, ents, row_ptr, col_ptr, nip,
+                                  (const long long*)pos, val, r, W, shc, shi0);
+    else hipLaunchKernelGGL((rs_primal_kernel<long long, false>), g, blk, lds, st, ents, row_ptr, col_ptr, nip,
+                            (const long long*)pos, val, r, W, shc, shi0);
+  }
+  LAUNCH_CHECK();
+  return 0;
+}
+
 int pml_rs_primal(int B, int dmax, const long long* ents, const long long* row_ptr, const long long* col_ptr,
                   const long long* nip, const void* pos, const double* val, const double* r, double* W,
                   void* stream, int pos32) {
-  if (B <= 0) return 0;
-  if (dmax < 0 || (size_t)dmax * sizeof(double) > 64 * 1024) return -22;
-  const size_t lds = (size_t)std::max(dmax, 1) * sizeof(double);
-  if (pos32)
-    hipLaunchKernelGGL(rs_primal_kernel<int>, dim3((unsigned)B), dim3(64), lds, (hipStream_t)stream, ents, row_ptr,
-                       col_ptr, nip, (const int*)pos, val, r, W);
-  else
-    hipLaunchKernelGGL(rs_primal_kernel<long long>, dim3((unsigned)B), dim3(64), lds, (hipStream_t)stream, ents,
-                       row_ptr, col_ptr, nip, (const long long*)pos, val, r, W);
-  LAUNCH_CHECK();
-  return 0;
+  return rs_primal_launch(B, dmax, ents, row_ptr, col_ptr, nip, pos, val, r, W, nullptr, nullptr, stream, pos32);
+}
+
+int pml_rs_primal_shift(int B, int dmax, const long long* ents, const long long* row_ptr, const long long* col_ptr,
+                        const long long* nip, const void* pos, const double* val, const double* r, double* W,
+                        const double* shc, const long long* shi0, void* stream, int pos32) {
+  if (shc == nullptr || shi0 == nullptr) return -22;
+  return rs_primal_launch(B, dmax, ents, row_ptr, col_ptr, nip, pos, val, r, W, shc, shi0, stream, pos32);
 }
 
 // ---- FULL coefficient variances (var_normal_kernel, var_scale_gram_kernel, chol_colnorm_kernel) ----

@@ -1301,8 +1301,16 @@ void re_tron_lean_kernel(ReTronArgs a) {
 // the row pointers two blocks ahead) are already in flight while a block computes. For d_e <= 32 (FH) the Hessian
 // at the trial point is formed inside the trial point's function evaluation; wider entities keep the Hessian
 // weights D per row and run a separate Hessian pass.
+// SHIFT: the entity's design matrix is X' = X (I - e_i0 c^T) (see re_tron_csr_kernel). The staged block is dense, so
+// the shifted rows are formed where they are staged: lane j < d_e keeps c_j in a register, and after the scatter (and
+// the wave fence it needs before anyone reads the block) rewrites its column of the 16 rows, Xs[r][j] -= Xs[r][i0]
+// c_j; lane i0 leaves its column alone (c_i0 = 0), so nobody writes what the others read. unstage then zeroes the
+// whole d_e columns of the block, not only the stored entries. Everything tron_dense_wave derives, it derives from
+// the staged block: margins (the true x . w), gradient, both Hessian variants, and the zero point's f / ||g|| behind
+// the tolerances, which it takes from an exact row pass at zero over the staged X' -- this kernel has no
+// ||X_e||_F ||c|| bound (xf2 is the lean kernel's and is not read here), so nothing is computed from stored values.
 // ============================================================================================================
-template <int T>
+template <int T, bool SHIFT = false>
 struct TallRows {
   static constexpr bool FH = T <= 2;
   static constexpr int XS = TronDenseCfg<T, FH>::XS, KE = T;     // KE entries per lane and row: rows of <= 16 T
@@ -1324,12 +1332,21 @@ struct TallRows {
   const long long e0;
   const uint16_t* const lcol;
   const double* const val;
+  // SHIFT: this lane's c_j (0 beyond d_e) and the intercept's column, clamped into the entity's range
+  double cj = 0.0;
+  int i0 = 0;
 
   __device__ __forceinline__ TallRows(const ReTronArgs& a_, int e)
       : a(a_), r0(a_.row_ptr[e]), nrows((int)(a_.row_ptr[e + 1] - r0)),
         nc((int)(a_.col_ptr[e + 1] - a_.col_ptr[e])), Wg(a_.W + a_.col_ptr[e]), D0(a_.scr), D1(a_.scr + a_.n_rows),
         Z0(a_.scr + 2 * a_.n_rows), Z1(a_.scr + 3 * a_.n_rows), e0(a_.nip[r0]), lcol(a_.lcol + e0),
-        val(a_.val + e0) {}
+        val(a_.val + e0) {
+    if constexpr (SHIFT) {
+      const int i = a_.ni0[e];
+      i0 = i < 0 ? 0 : (i < nc ? i : nc - 1);
+      cj = lane < nc && lane != i0 ? a_.nc[a_.col_ptr[e] + lane] : 0.0;
+    }
+  }
 
   // row pointers of block b (lane q <= TRON_RB: entity-local offset of row b + q)
   __device__ __forceinline__ int fetch(int b) const {
@@ -1365,17 +1382,36 @@ struct TallRows {
       for (int k = 0; k < KE; ++k)
         if (B.c[u][k] >= 0) Xs[(u * 4 + grp) * XS + B.c[u][k]] = ZERO ? 0.0 : B.v[u][k];
   }
-  __device__ __forceinline__ void stage(const Blk& B, double* Xs) const { scatter<false>(B, Xs); }
-  __device__ __forceinline__ void unstage(const Blk& B, double* Xs) const { scatter<true>(B, Xs); }
+  __device__ __forceinline__ void stage(const Blk& B, double* Xs) const {
+    scatter<false>(B, Xs);
+    if constexpr (SHIFT) {
+      wave_sync();
+      if (lane < nc && lane != i0) {
+#pragma unroll 4
+        for (int r = 0; r < TRON_RB; ++r) Xs[r * XS + lane] = fma(-Xs[r * XS + i0], cj, Xs[r * XS + lane]);
+      }
+    }
+  }
+  __device__ __forceinline__ void unstage(const Blk& B, double* Xs) const {
+    if constexpr (SHIFT) {
+      if (lane < nc) {
+#pragma unroll 4
+        for (int r = 0; r < TRON_RB; ++r) Xs[r * XS + lane] = 0.0;
+      }
+      wave_sync();                                 // before the next block's scatter, by other lanes, into these slots
+    } else {
+      scatter<true>(B, Xs);
+    }
+  }
 };
 
-template <int T, int LOSS>
+template <int T, int LOSS, bool SHIFT = false>
 __global__ __launch_bounds__(64) void re_tron_tall_kernel(ReTronArgs a) {
-  using C = TronDenseCfg<T, TallRows<T>::FH>;
+  using C = TronDenseCfg<T, TallRows<T, SHIFT>::FH>;
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int e = a.order[blockIdx.x];
   for (int i = threadIdx.x; i < TRON_RB * C::XS; i += 64) smem[C::XOFF + i] = 0.0;    // the staged block starts empty
-  tron_dense_wave<T, LOSS>(a, e, TallRows<T>(a, e), smem);
+  tron_dense_wave<T, LOSS>(a, e, TallRows<T, SHIFT>(a, e), smem);
 }
 
 // ============================================================================================================
@@ -2156,6 +2192,33 @@ int pml_re_tron_hess(const int* order, int n_launch, const long long* row_ptr, c
       case 2: hipLaunchKernelGGL((re_tron_tall_kernel<2, L()>), dim3(n_launch), dim3(64), smem, st, a); break;
       case 3: hipLaunchKernelGGL((re_tron_tall_kernel<3, L()>), dim3(n_launch), dim3(64), smem, st, a); break;
       default: hipLaunchKernelGGL((re_tron_tall_kernel<4, L()>), dim3(n_launch), dim3(64), smem, st, a); break;
+    }
+  });
+  LAUNCH_CHECK();
+  return 0;
+}
+
+// pml_re_tron_hess with a normalization shift (re_tron_tall_kernel<T, LOSS, true>): ``nc`` / ``ni0`` as for
+// pml_re_tron_csr_shift. Same LDS as without a shift (c_j lives in a register of lane j).
+int pml_re_tron_hess_shift(const int* order, int n_launch, const long long* row_ptr, const long long* col_ptr,
+                           const long long* nip, const uint16_t* lcol, const double* val, const double* y,
+                           const double* off, const double* wt, double* scr, long long n_rows, double* W, double* f,
+                           int* iters, int* reason, double* zout, int* npass, int loss, double l2, double tol,
+                           int max_iter, int max_fail, int max_cg, int dp, const double* nc, const int* ni0,
+                           hipStream_t st) {
+  if (n_launch <= 0) return 0;
+  if (dp < 16 || dp > 64 || dp % 16 || loss < 0 || loss > 2 || nc == nullptr || ni0 == nullptr) return -22;
+  const size_t smem = pml_re_tron_hess_smem(dp);
+  ReTronArgs a{order, n_launch, row_ptr, col_ptr, nip, lcol, val, y, off, wt, scr, n_rows, W, f, iters, reason,
+               zout, npass, loss, l2, tol, max_iter, max_fail, max_cg, dp};
+  a.nc = nc;
+  a.ni0 = ni0;
+  with_loss(loss, [&](auto L) {
+    switch (dp / 16) {
+      case 1: hipLaunchKernelGGL((re_tron_tall_kernel<1, L(), true>), dim3(n_launch), dim3(64), smem, st, a); break;
+      case 2: hipLaunchKernelGGL((re_tron_tall_kernel<2, L(), true>), dim3(n_launch), dim3(64), smem, st, a); break;
+      case 3: hipLaunchKernelGGL((re_tron_tall_kernel<3, L(), true>), dim3(n_launch), dim3(64), smem, st, a); break;
+      default: hipLaunchKernelGGL((re_tron_tall_kernel<4, L(), true>), dim3(n_launch), dim3(64), smem, st, a); break;
     }
   });
   LAUNCH_CHECK();

@@ -791,6 +791,10 @@ def game_lib() -> Optional[ctypes.CDLL]:
         lib.pml_seg_gram_set_s.argtypes = [c_int]
         lib.pml_rs_primal.argtypes = [c_int, c_int] + [c_void_p] * 9 + [c_int]
         lib.pml_rs_primal.restype = c_int
+        lib.pml_seg_gram_shift.argtypes = [c_int, c_int, c_int, ctypes.c_longlong] + [c_void_p] * 10
+        lib.pml_seg_gram_shift.restype = c_int
+        lib.pml_rs_primal_shift.argtypes = [c_int, c_int] + [c_void_p] * 11 + [c_int]
+        lib.pml_rs_primal_shift.restype = c_int
         lib.pml_var_mmax.argtypes = []
         lib.pml_var_mmax.restype = c_int
         lib.pml_chol_colnorm_lds.argtypes = [c_int, c_int]
@@ -1247,17 +1251,26 @@ SEG_GRAM_DMAX = 160 * 1024 // 8      # seg_gram_kernel's LDS image: one fp64 per
 
 def seg_gram(ents: torch.Tensor, n: int, row_ptr: torch.Tensor, col_ptr: torch.Tensor, nip: torch.Tensor,
              pos: torch.Tensor, val: torch.Tensor, dmax: Optional[int] = None,
-             maxnnz: Optional[int] = None) -> torch.Tensor:
+             maxnnz: Optional[int] = None, shift=None) -> torch.Tensor:
     """Per-entity Gram matrices ``K [B, n, n]`` (``seg_gram_kernel``) of the entities ``ents`` of a block-diagonal
     CSR (rows grouped by entity: ``row_ptr``; entity column ranges: ``col_ptr``; ``nip/pos/val`` = int64 indptr,
     int64 global columns, fp64 values, distinct columns per row). Entities with fewer than ``n`` rows are zero
-    padded. Every entity needs ``d_e <= SEG_GRAM_DMAX`` (LDS image). Device only."""
+    padded. Every entity needs ``d_e <= SEG_GRAM_DMAX`` (LDS image). ``shift`` = ``(c, i0)`` (``c`` fp64 per packed
+    column of ``col_ptr``, ``i0`` per entity of ``col_ptr``: the intercept's entity-local column, ``c[i0] = 0``):
+    ``K' = X' X'^T`` of ``X' = X (I - e_i0 c^T)``, formed from the shifted rows (``seg_gram_kernel<S, STAGE, true>``;
+    the LDS then also holds ``c_e``: ``2 d_e + n`` doubles must fit 160 KB). Device only."""
     lib = require_game_lib()
     dev = ents.device
     B = int(ents.numel())
     K = torch.empty(B, n, n, dtype=torch.float64, device=dev)
     if B == 0:
         return K
+    if shift is not None:
+        sc = shift[0].to(dev, torch.float64).contiguous()
+        si0 = shift[1].to(dev, torch.int64).contiguous()
+        if os.environ.get("PML_CHECK_KERNEL_INPUTS", "0") == "1":
+            check_re_shift_inputs(ents, col_ptr.to(dev), sc, si0)
+        assert sc.numel() >= int(col_ptr[-1]) and si0.numel() == col_ptr.numel() - 1
     t = [x.to(dev).contiguous() for x in (ents, row_ptr, col_ptr, nip, pos)]
     for x in t[:4]:
         assert x.dtype == torch.int64
@@ -1271,6 +1284,13 @@ def seg_gram(ents: torch.Tensor, n: int, row_ptr: torch.Tensor, col_ptr: torch.T
     if dmax > SEG_GRAM_DMAX:
         raise ValueError(f"seg_gram: an entity has {dmax} > {SEG_GRAM_DMAX} projected columns")
     stage = int(maxnnz) if os.environ.get("PML_SEG_GRAM_STAGE", "1") != "0" else 0
+    if shift is not None:
+        if (2 * dmax + n) * 8 > 160 * 1024:
+            raise ValueError(f"seg_gram: an entity of {dmax} projected columns is too wide for the shifted image")
+        check(lib.pml_seg_gram_shift(B, n, dmax, stage, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(),
+                                     t[3].data_ptr(), t[4].data_ptr(), v.data_ptr(), K.data_ptr(), sc.data_ptr(),
+                                     si0.data_ptr(), stream_handle(dev)), "seg_gram_shift")
+        return K
     check(lib.pml_seg_gram(B, n, dmax, stage, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(),
                            t[4].data_ptr(), v.data_ptr(), K.data_ptr(), stream_handle(dev)), "seg_gram")
     return K
@@ -1303,11 +1323,14 @@ def batched_cholesky(K: torch.Tensor, nv: torch.Tensor):
 RS_PRIMAL_DMAX = 64 * 1024 // 8     # rs_primal_kernel: one fp64 LDS slot per projected column of the entity
 
 
-def rs_primal(ents: torch.Tensor, row_ptr, col_ptr, nip, pos, val, r: torch.Tensor, W: torch.Tensor) -> None:
+def rs_primal(ents: torch.Tensor, row_ptr, col_ptr, nip, pos, val, r: torch.Tensor, W: torch.Tensor,
+              shift=None) -> None:
     """``W[col_ptr[e]:col_ptr[e+1]] = X_e^T r[rows of e]`` for the entities ``ents`` (int64) of a block-diagonal
     CSR (``nip``/``pos``/``val``: int64 indptr, int64 or int32 global columns, fp64 values; columns of an entity inside
     its ``col_ptr`` range, distinct inside a row) — ``rs_primal_kernel``, one wave per entity. In place on ``W``
-    (fp64, packed like ``col_ptr``); every entity needs ``d_e <= RS_PRIMAL_DMAX``. Device only."""
+    (fp64, packed like ``col_ptr``); every entity needs ``d_e <= RS_PRIMAL_DMAX``. ``shift`` = ``(c, i0)`` (``c`` fp64
+    packed like ``W``, ``i0`` int64 per entity of ``col_ptr``, ``c[i0] = 0``): ``X'_e^T r = X_e^T r - c_e (x0 . r)``
+    with ``x0`` the stored column ``i0`` (``rs_primal_kernel<PT, true>``). Device only."""
     lib = require_game_lib()
     dev = W.device
     B = int(ents.numel())
@@ -1323,6 +1346,19 @@ def rs_primal(ents: torch.Tensor, row_ptr, col_ptr, nip, pos, val, r: torch.Tens
     dmax = int((col_ptr[ents + 1] - col_ptr[ents]).max())
     if dmax > RS_PRIMAL_DMAX:
         raise ValueError(f"rs_primal: an entity has {dmax} > {RS_PRIMAL_DMAX} projected columns")
+    if shift is not None:
+        sc, si0 = shift
+        if os.environ.get("PML_CHECK_KERNEL_INPUTS", "0") == "1":
+            check_re_shift_inputs(ents, t[2], sc, si0)
+        for x in (sc, si0):
+            assert x.is_cuda and x.is_contiguous() and x.device == dev
+        assert sc.dtype == torch.float64 and sc.numel() >= W.numel()
+        assert si0.dtype == torch.int64 and si0.numel() == col_ptr.numel() - 1
+        check(lib.pml_rs_primal_shift(B, dmax, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(),
+                                      t[4].data_ptr(), v.data_ptr(), r.data_ptr(), W.data_ptr(), sc.data_ptr(),
+                                      si0.data_ptr(), stream_handle(dev), int(t[4].dtype == torch.int32)),
+              "rs_primal_shift")
+        return
     check(lib.pml_rs_primal(B, dmax, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(),
                             t[4].data_ptr(), v.data_ptr(), r.data_ptr(), W.data_ptr(), stream_handle(dev),
                             int(t[4].dtype == torch.int32)),
@@ -1683,6 +1719,8 @@ def re_lib() -> Optional[ctypes.CDLL]:
         lib.pml_re_tron_csr.restype = c_int
         lib.pml_re_tron_csr_shift.argtypes = lib.pml_re_tron_csr.argtypes[:-1] + [c_void_p, c_void_p, c_void_p]
         lib.pml_re_tron_csr_shift.restype = c_int
+        lib.pml_re_tron_hess_shift.argtypes = lib.pml_re_tron_csr_shift.argtypes
+        lib.pml_re_tron_hess_shift.restype = c_int
         lib.pml_re_tron_smem.argtypes = [c_int]
         lib.pml_re_tron_smem.restype = ctypes.c_size_t
         lib.pml_re_tron_hess.argtypes = lib.pml_re_tron_csr.argtypes
@@ -1775,14 +1813,14 @@ def re_tron_csr(order, row_ptr, col_ptr, nip, lcol, val, y, off, wt, scr, W, f, 
     fp64 per entity): ``||X_e||_F^2``; a warm start then scales its gradient tolerance by the bound
     ``||X_e||_F ||c||`` of ``||g(0)||`` and runs the pass at zero only if a gradient norm reaches it. ``shift`` =
     ``(c, i0)`` (fp64 packed like ``W``; int32 per entity, the entity-local intercept column): the entity's design
-    matrix is ``X (I - e_i0 c^T)`` (``re_tron_csr_kernel<LOSS, true>``: the streaming kernel only, not ``hessian``
-    / ``lean``). ``narrow`` = ``(precision, nip, cols, rec)`` (lean only): the launch reads its rows from this narrow
+    matrix is ``X (I - e_i0 c^T)`` (``re_tron_csr_kernel<LOSS, true>``, or with ``hessian`` ``re_tron_tall_kernel<T,
+    LOSS, true>``, which forms the shifted rows in its staged block; not ``lean``). ``narrow`` = ``(precision, nip, cols, rec)`` (lean only): the launch reads its rows from this narrow
     quad stream (:func:`csr_gather_quads`; ``precision`` ``"f32"`` / ``"bf16"``, ``nip`` int64 over the same rows in
     multiples of 4) with ``re_tron_lean_kernel<LOSS, J, true, VT>`` instead of ``nip`` / ``lcol`` / ``val``. Device
     only; in place, nothing returned."""
     if shift is not None:
-        if hessian or lean:
-            raise ValueError("re_tron_csr: a shift runs on the streaming kernel only (not hessian / lean)")
+        if lean:
+            raise ValueError("re_tron_csr: a shift runs on the streaming or the tall kernel only (not lean)")
         lean = False
         sc, si0 = shift
         if os.environ.get("PML_CHECK_KERNEL_INPUTS", "0") == "1":
@@ -1854,8 +1892,8 @@ def re_tron_csr(order, row_ptr, col_ptr, nip, lcol, val, y, off, wt, scr, W, f, 
             assert t.is_cuda and t.is_contiguous() and t.device == W.device
         assert sc.dtype == torch.float64 and sc.numel() == W.numel()
         assert si0.dtype == torch.int32 and si0.numel() == n_ent
-        check(lib.pml_re_tron_csr_shift(*args, sc.data_ptr(), si0.data_ptr(), stream_handle(W.device)),
-              "re_tron_csr_shift")
+        fn = lib.pml_re_tron_hess_shift if hessian else lib.pml_re_tron_csr_shift
+        check(fn(*args, sc.data_ptr(), si0.data_ptr(), stream_handle(W.device)), "re_tron_csr_shift")
         return
     assert narrow is None, "a narrow quad stream is read by the lean kernel only"
     fn = lib.pml_re_tron_hess if hessian else lib.pml_re_tron_csr

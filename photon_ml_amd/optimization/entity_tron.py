@@ -112,7 +112,9 @@ class EntityTronBatch:
 
     When the data carries a normalization shift (``seg.shift``) every class, dm <= 1024 included, launches
     ``re_tron_csr_kernel<LOSS, true>`` with the batch's own ``c`` (gathered by ``cols``) and per-entity intercept
-    column; the lean, tall, Hessian and resident kernels are never launched.
+    column; the lean, tall, Hessian and resident kernels are never launched. With ``shift_tall`` (the coordinate's
+    ``shift_routes="auto"``) the entities of ``d_e <= HESS_DMAX`` launch ``re_tron_tall_kernel<T, LOSS, true>`` with the
+    same ``(c, i0)`` instead; the rest stay as described.
 
     Narrow storage (``ds.config.storage_precision`` ``f32`` / ``bf16``, GPU, no shift): the gathered copy is split in
     two complementary streams over the same batch rows. The LEAN entities (64 < d_e <= ``RE_LEAN_DMAX``, not
@@ -122,7 +124,7 @@ class EntityTronBatch:
     launches read the narrow stream (``re_tron_lean_kernel<LOSS, J, true, VT>``), all others the fp64 one; ``row_ptr``,
     ``y``, ``w``, offsets, ``scr``, ``z`` and ``gsc`` are shared. :meth:`stream_bytes` reports what each stream holds."""
 
-    def __init__(self, ds, mask: torch.Tensor):
+    def __init__(self, ds, mask: torch.Tensor, shift_tall: bool = False):
         seg = ds.seg
         dev = seg.y.device
         shifted = getattr(seg, "shift", None) is not None
@@ -174,7 +176,7 @@ class EntityTronBatch:
         row_ent = torch.repeat_interleave(torch.arange(self.B, device=dev), ne, output_size=n_rows)
         # Entities of at most HESS_DMAX coefficients (tall: the row space took the wide ones) run the exact-Hessian
         # kernel (MFMA), the others the sparse Hessian-vector kernel.
-        hess = (de <= HESS_DMAX) & (not shifted)
+        hess = (de <= HESS_DMAX) & (not shifted or bool(shift_tall))
         stream_sel = ~hess
         if dev.type == "cuda":
             # the batch's rows straight from the parent CSR by one gather kernel (entity-local int16 columns, rows
@@ -364,7 +366,7 @@ class EntityTronBatch:
             if self.shift is not None:
                 re_tron_csr(order, self.row_ptr, self.col_ptr, self.nip, self.lcol, self.val, self.y, off, self.w,
                             self.scr, W, f, iters, reason, z, loss.loss_id, l2, tol, max_iter, max_fail, max_cg, dm,
-                            lean=False, shift=self.shift)
+                            hessian=is_h, lean=False, shift=self.shift)
                 continue
             re_tron_csr(order, self.row_ptr, self.col_ptr, self.nip, self.lcol, self.val, self.y, off, self.w,
                         self.scr, W, f, iters, reason, z, loss.loss_id, l2, tol, max_iter, max_fail, max_cg, dm,

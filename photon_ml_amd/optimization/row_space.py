@@ -72,8 +72,8 @@ def _canonical_csr(csr, dev):
 
 
 def row_space_eligible(l1: float, constraints=None, shift: bool = False) -> bool:
-    """``shift``: the data carries a normalization shift (``SegmentedGLMData.shift``), which the row-space Gram
-    matrices do not include."""
+    """``shift``: the data carries a normalization shift (``SegmentedGLMData.shift``) that the caller's batch will not
+    include (``RowSpaceBatch(..., shift=)`` includes it: such a caller passes False)."""
     return l1 == 0 and not constraints and not shift
 
 
@@ -121,15 +121,29 @@ class RowSpaceBatch:
     matrix (every Cholesky pivot above :data:`RS_PIVOT_RTOL` times its diagonal entry), as dense padded batches
     per size class (:data:`SIZE_CLASSES`). Row-space coefficients of all classes are packed into one flat vector
     (class after class, ``[B_c, n_c]`` row-major each); ``ents``, ``valid`` and the solver results follow the same
-    order."""
+    order.
 
-    def __init__(self, seg, nmax: int = 64, csr=None):
+    ``shift`` = ``seg.shift`` = ``(c, i0)``: the batch is that of ``X' = X (I - e_i0 c^T)``. Only its two ends know:
+    the Gram kernel writes ``K' = X' X'^T`` (``seg_gram(..., shift=)``) and the back-map applies ``X'^T``
+    (``rs_primal(..., shift=)``); the factors, the solves, the margins ``L' beta`` and ``||w'||^2 = ||beta||^2`` in
+    between only ever see ``L'``. Under a shift the batch takes only entities with an intercept (``i0 >= 0``), at most
+    ``min(SEG_GRAM_DMAX, RS_PRIMAL_DMAX)`` coefficients and a canonical device CSR: there are no indicator-pass Gram
+    columns and no shard-wide transpose fallback, and an entity that would need either is left to the caller."""
+
+    def __init__(self, seg, nmax: int = 64, csr=None, shift=None):
         nmax = min(int(nmax), ROW_SPACE_NMAX)
         self.seg = seg
+        self.shift = shift
         dev = seg.y.device
         n_e = seg.row_ptr[1:] - seg.row_ptr[:-1]
         d_e = seg.col_ptr[1:] - seg.col_ptr[:-1]
         cand = (n_e > 0) & (n_e <= nmax) & (n_e <= d_e)
+        if shift is not None:
+            from ..ops.native import RS_PRIMAL_DMAX, SEG_GRAM_DMAX
+            csr = _canonical_csr(csr, dev) if dev.type == "cuda" else None
+            if csr is None:
+                cand &= False
+            cand &= (shift[1].to(dev) >= 0) & (d_e <= min(SEG_GRAM_DMAX, RS_PRIMAL_DMAX))
         if nmax > 64 and csr is not None:
             # beyond 64 rows a row-space CG step (two LDS-resident triangular mat-vecs, ~n^2 / 2 FMAs each) pays
             # only when the entity's rows are dense enough: measured break-even on game5pl-like entities at ~0.5 n
@@ -159,7 +173,8 @@ class RowSpaceBatch:
         from ..ops.native import sorted_counts
         cnt = sorted_counts(cls_of[order], bounds.numel()).tolist()
         de_s = d_e[ents_s]
-        csr = _canonical_csr(csr, dev) if dev.type == "cuda" else None
+        if shift is None:
+            csr = _canonical_csr(csr, dev) if dev.type == "cuda" else None
         if csr is not None:
             enz_s = csr[0][seg.row_ptr[ents_s + 1]] - csr[0][seg.row_ptr[ents_s]]
         spans, lo = [], 0
@@ -191,7 +206,7 @@ class RowSpaceBatch:
             for gi, (e, n, valid, rows, _, ne, st) in enumerate(geo):
                 if int(st[1]) <= SEG_GRAM_DMAX:
                     geo[gi] = (e, n, valid, rows, seg_gram(e, n, seg.row_ptr, seg.col_ptr, *csr, dmax=int(st[1]),
-                                                            maxnnz=int(st[2])), ne, st)
+                                                            maxnnz=int(st[2]), shift=shift), ne, st)
                     continue
                 ok = d_e[e] <= SEG_GRAM_DMAX
                 K = torch.zeros(e.numel(), n, n, dtype=torch.float64, device=dev)
@@ -276,6 +291,12 @@ class RowSpaceBatch:
         # slot of every compact back-map row in the packed solution: the back-map gathers its row weights straight
         # from L^-T beta (no zero-filled per-row vector, scatter and gather over the whole coordinate)
         self._primal_slot = None
+        self._primal_shift = None
+        if shift is not None and self.B:
+            # (c packed like W, i0 per entity of the compact list's interleaved ranges: odd slots are no entities)
+            i0c = torch.full((2 * self.B,), -1, dtype=torch.int64, device=dev)
+            i0c[0::2] = shift[1].to(dev, torch.int64)[self.ents]
+            self._primal_shift = (shift[0].to(dev, torch.float64).contiguous(), i0c)
         if self._primal_csr is not None:
             slot_of_row = torch.full((seg.y.numel(),), -1, dtype=torch.int64, device=dev)
             slot_of_row[self.vrow] = self.vslot
@@ -339,7 +360,7 @@ class RowSpaceBatch:
 
     def beta_from_primal(self, W: torch.Tensor) -> torch.Tensor:
         """Orthogonal projection of primal coefficients onto the row space: beta = L^{-1} X w (packed)."""
-        z = self._slots(self.seg.glm.matvec(W))
+        z = self._slots(self.seg.xw(W))                                  # X' w under a shift
         return torch.cat([_btrsv(c.L, c.view(z)).reshape(-1) for c in self.classes])
 
     def _alpha(self, beta: torch.Tensor) -> Optional[torch.Tensor]:
@@ -367,8 +388,10 @@ class RowSpaceBatch:
             ents2, row_ptr, col_ptr, nip, pos, val, rows = pc
             d_total = int(self.seg.col_ptr[-1])
             W = (torch.zeros if fill else torch.empty)(d_total, dtype=torch.float64, device=beta.device)
-            rs_primal(ents2, row_ptr, col_ptr, nip, pos, val, alpha[self._primal_slot], W)
+            rs_primal(ents2, row_ptr, col_ptr, nip, pos, val, alpha[self._primal_slot], W,
+                      shift=getattr(self, "_primal_shift", None))
             return W
+        assert getattr(self, "shift", None) is None or alpha is None, "a shifted batch maps back by rs_primal only"
         r = torch.zeros(self.seg.y.numel(), dtype=torch.float64, device=beta.device)
         if alpha is not None:
             r[self.vrow] = alpha[self.vslot]
