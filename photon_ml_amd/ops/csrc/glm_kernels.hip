@@ -1454,37 +1454,91 @@ __global__ __launch_bounds__(256, 5) void tl_tg_kernel(const int* __restrict__ g
   tl_t_group<VT, XT, SQ, PT>(groups + TL_TG_COLS * blockIdx.x, pack, val, nar, x, G, dim, parts, acc);
 }
 
-// Shard-wide: the groups AND the items of every chunk in ONE launch -- blocks [0, ngroups) run the groups (the long
-// units first), the others the items exactly as tl_t_multi_kernel<VT, XT, double, SQ, 1024, 2, 4, 3> does (tl_t_item on
-// the same 32 KB viewed as 4 wave rows). Measured against a launch of its own for the groups: the items fill the CUs
-// that the last long groups leave idle (headline 33.3-33.6 vs 34.3 ms/step, profiles/tl_t_groups.md). Stream pointers
-// as in tl_fwd_multi_kernel, gated like tl_t_multi_kernel; live / live_g: optional flags per item / per group.
+// Shard-wide: the groups AND the items of every chunk in ONE launch, the items exactly as
+// tl_t_multi_kernel<VT, XT, double, SQ, 1024, 2, 4, 3> runs them (tl_t_item on the same 32 KB viewed as 4 wave rows).
+// A unit is named by one number u: u < ngroups is group u (the table holds the long groups first), any other u is
+// item u - ngroups. Which units are resident together is the one thing the two schedules below decide; what a unit
+// computes and where it writes depends on the unit alone, so G is bit for bit the same under every schedule. A group
+// has one wave gathering in its wide phases and waits on latency, an item has four and loads the address path: a CU
+// that holds both kinds hides the items' gathers under the groups' waits (profiles/tl_tg_sched.md).
+//   static (TL_TG_SCHED 0): one work-group per unit, block i runs unit tl_tg_interleave(i): windows of a + b blocks
+//     take a groups and b items while full windows of both remain, then the groups left, then the items left
+//     (a : b = 5 : 0 is "the groups, then the items"). This fixes the dispatch order only.
+//   persistent (TL_TG_SCHED 1): 5 work-groups per CU, each looping over units it draws from two ticket counters
+//     (tickets[0]: groups, tickets[1]: items; zeroed on the stream before every launch). Slot blockIdx.x % 5 draws
+//     from the groups when it is below k, else from the items, and moves to the other counter for good once its own
+//     has run out; with both run out it returns. Nothing guarantees that the five slots of one residue class share
+//     a CU: the policy only needs the device-wide share of resident groups to stay near k / 5. No work-group waits
+//     on another. The ticket is drawn by thread 0 and broadcast through acc[0] (LDS holds nothing but acc: 5 x 32 KB
+//     fill the CU), between a barrier after the last unit's reads of acc and one before the next unit zeroes it.
+// Stream pointers as in tl_fwd_multi_kernel, gated like tl_t_multi_kernel; live / live_g: optional flags per item /
+// per group (a skipped unit uses up its ticket).
+#define TL_TG_SLOTS 5    // work-groups per CU: __launch_bounds__(256, 5), 32 KB of LDS each
+#define TL_TG_NONE 0xffffffffu
+__device__ __forceinline__ int tl_tg_interleave(int i, int ng, int ni, int a, int b) {
+  if (b <= 0 || a < 0) return i;                               // the groups, then the items
+  if (a == 0) return i < ni ? ng + i : i - ni;                 // the items, then the groups
+  const int w = a + b, nw = ng / a < ni / b ? ng / a : ni / b;  // full windows of both kinds
+  if (i < nw * w) {
+    const int win = i / w, p = i - win * w;
+    return p < a ? win * a + p : ng + win * b + (p - a);
+  }
+  const int j = i - nw * w, rg = ng - nw * a;
+  return j < rg ? nw * a + j : ng + nw * b + (j - rg);
+}
+
 template <typename VT, typename XT, bool SQ, int PT>
-__global__ __launch_bounds__(256, 5) void tl_tg_multi_kernel(const int* __restrict__ groups, int ngroups,
-                                                              const int* __restrict__ items,
+__global__ __launch_bounds__(256, TL_TG_SLOTS) void tl_tg_multi_kernel(const int* __restrict__ groups, int ngroups,
+                                                              const int* __restrict__ items, int nitems,
                                                               const unsigned long long* __restrict__ ptrs,
                                                               const XT* __restrict__ x, double* __restrict__ G, int dim,
                                                               double* __restrict__ parts,
                                                               const unsigned char* __restrict__ live,
                                                               const unsigned char* __restrict__ live_g,
-                                                              const int* __restrict__ gate) {
+                                                              const int* __restrict__ gate, unsigned* tickets,
+                                                              int sched, int ka, int kb) {
   __shared__ double acc[1 << TL_TG_BITS];     // exactly 32 KB, nothing else in LDS
   if (gate && *gate == 0) return;
-  const int b = __builtin_amdgcn_readfirstlane(blockIdx.x);
-  if (b < ngroups) {
-    if (live_g && !live_g[b]) return;
-    const int* q = groups + TL_TG_COLS * b;
-    const unsigned long long* pc = ptrs + 6 * q[21];
-    const TLNarrow nar = {(const uint16_t*)pc[2], (const void*)pc[3], (const int*)pc[4], nullptr};
-    tl_t_group<VT, XT, SQ, PT>(q, (const uint32_t*)pc[0], (const VT*)pc[1], nar, x + q[22], G, dim, parts, acc);
-  } else {
-    if (live && !live[b - ngroups]) return;
-    const int* q = items + 8 * (b - ngroups);
-    const unsigned long long* pc = ptrs + 6 * q[0];
-    const TLNarrow nar = {(const uint16_t*)pc[2], (const void*)pc[3], (const int*)pc[4], (const int*)pc[5]};
-    tl_t_item<VT, XT, double, SQ, 1 << TL_TG_SUB, 2, 4, 3>(q[1], q[2], q[3], q[4], q[6], q[7], TL_TG_SUB,
-                                                         (const uint32_t*)pc[0], (const VT*)pc[1], nar, x + q[5], G,
-                                                         dim, parts, (double(*)[1 << TL_TG_SUB])acc);
+  const bool persistent = sched != 0;
+  int queue = (int)(blockIdx.x % TL_TG_SLOTS) < ka ? 0 : 1, left = 2;   // thread 0: its counter, counters not run out
+  for (bool first = true;; first = false) {
+    unsigned u;
+    if (persistent) {
+      __syncthreads();                         // every wave is done with the last unit's acc
+      if (threadIdx.x == 0) {
+        unsigned code = TL_TG_NONE;
+        while (left > 0) {
+          const unsigned t = atomicAdd(tickets + queue, 1u);
+          if (t < (unsigned)(queue ? nitems : ngroups)) { code = queue ? ngroups + t : t; break; }
+          queue ^= 1;
+          --left;
+        }
+        *(volatile unsigned*)acc = code;
+      }
+      __syncthreads();
+      u = *(const volatile unsigned*)acc;
+      __syncthreads();                         // ... and has read the ticket before the unit zeroes acc
+      if (u == TL_TG_NONE) return;
+    } else {
+      if (!first) return;
+      u = tl_tg_interleave(blockIdx.x, ngroups, nitems, ka, kb);
+    }
+    const int b = __builtin_amdgcn_readfirstlane((int)u);
+    if (b < ngroups) {
+      if (live_g && !live_g[b]) continue;
+      const int* q = groups + TL_TG_COLS * b;
+      const unsigned long long* pc = ptrs + 6 * q[21];
+      const TLNarrow nar = {(const uint16_t*)pc[2], (const void*)pc[3], (const int*)pc[4], nullptr};
+      tl_t_group<VT, XT, SQ, PT>(q, (const uint32_t*)pc[0], (const VT*)pc[1], nar, x + q[22], G, dim, parts, acc);
+    } else {
+      if (live && !live[b - ngroups]) continue;
+      const int* q = items + 8 * (b - ngroups);
+      const unsigned long long* pc = ptrs + 6 * q[0];
+      const TLNarrow nar = {(const uint16_t*)pc[2], (const void*)pc[3], (const int*)pc[4], (const int*)pc[5]};
+      tl_t_item<VT, XT, double, SQ, 1 << TL_TG_SUB, 2, 4, 3>(q[1], q[2], q[3], q[4], q[6], q[7], TL_TG_SUB,
+                                                           (const uint32_t*)pc[0], (const VT*)pc[1], nar, x + q[5], G,
+                                                           dim, parts, (double(*)[1 << TL_TG_SUB])acc);
+    }
   }
 }
 
@@ -1580,6 +1634,7 @@ struct TLTMultiDesc {
   const unsigned char* live_mt;
   const int* groups; int ngroups; // tile groups of every chunk (tl_tg_multi_kernel) and their optional live flags
   const unsigned char* live_g;
+  unsigned* tickets;              // two unit counters of the persistent tl_tg_multi_kernel (the descriptor's owner's)
 };
 
 // Runtime TL configuration (pml_tl_config; read by the experiment build's launch ladder only, see TL_EXPERIMENT):
@@ -1635,6 +1690,14 @@ static int g_rs_variant = 5;   // rs_tron variant: 0-2 rs_tron_kernel<V>; for n 
                                 // (scripts/rs_tron_bench.py, profiles/rs_tron_roofline.md)
 static int g_tl_deep = 0;      // interleaved forward: 0 two-slot pipeline (P = 3), 1 deep S4/D1 (P = 5), 2 S6/D2 (P = 6)
 static int g_tl_deep_t = 0;    // interleaved transpose: same
+// Schedule of tl_tg_multi_kernel (see there): production compiles TL_TG_SCHED with TL_TG_K resident group slots of 5
+// (persistent) or TL_TG_A : TL_TG_B (static); the experiment build reads pml_tl_set_tg_sched instead (b < 0 with the
+// static schedule: a : b in the proportion ngroups : nitems, on windows of 8).
+#define TL_TG_SCHED 1
+#define TL_TG_K 4
+#define TL_TG_A 5
+#define TL_TG_B 0
+static int g_tg_sched = TL_TG_SCHED, g_tg_a = TL_TG_SCHED ? TL_TG_K : TL_TG_A, g_tg_b = TL_TG_B;
 
 // The production build instantiates only the kernels it can launch: the production stream pipelines (interleaved
 // layout: P = 3, plain: P = 0), the production wave counts (forward 2, transpose 4) and the accumulators of
@@ -1824,13 +1887,40 @@ static int tl_t_impl(const TLTDesc* c, const void* x, double* G, double* parts, 
   return tl_t_combine(c, G, parts, st);
 }
 
+// Compute units of the current device, asked once per device.
+static int tl_cu_count() {
+  static int ncu[64] = {0};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+  if (ncu[dev] == 0) {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
+    ncu[dev] = prop.multiProcessorCount;
+  }
+  return ncu[dev];
+}
+
 template <typename VT, typename XT, bool SQ>
 static int tl_t_multi_impl(const TLTMultiDesc* c, const void* x, double* G, double* parts, hipStream_t st) {
   if (c->ngroups > 0) {      // groups and items in one launch (tl_tg_multi_kernel)
+    const int ni = c->nitems > 0 ? c->nitems : 0;
+    const int sched = TL_EXPERIMENT ? g_tg_sched : TL_TG_SCHED;
+    int ka = TL_EXPERIMENT ? g_tg_a : (TL_TG_SCHED ? TL_TG_K : TL_TG_A), kb = TL_EXPERIMENT ? g_tg_b : TL_TG_B;
+    int grid = c->ngroups + ni;
+    if (sched) {             // persistent: TL_TG_SLOTS work-groups per CU over two zeroed ticket counters
+      const int ncu = tl_cu_count();
+      if (!c->tickets || ncu <= 0) return -22;
+      if (hipMemsetAsync(c->tickets, 0, 2 * sizeof(unsigned), st) != hipSuccess) return -5;
+      grid = TL_TG_SLOTS * ncu;
+    } else if (kb < 0) {     // proportional static interleave
+      ka = (8 * c->ngroups + (c->ngroups + ni) / 2) / (c->ngroups + ni);
+      ka = ka < 1 ? 1 : (ka > 7 ? 7 : ka);
+      kb = ni > 0 ? 8 - ka : 0;
+    }
     const int rt = tl_with_tg<XT>(c->cbits, c->il, [&](auto pt) {
-      hipLaunchKernelGGL((tl_tg_multi_kernel<VT, XT, SQ, decltype(pt)::value>), dim3(c->ngroups + (c->nitems > 0 ? c->nitems : 0)),
-                         dim3(256), 0, st, c->groups, c->ngroups, c->items, c->ptrs, (const XT*)x, G, c->dim, parts,
-                         c->live, c->live_g, g_gate);
+      hipLaunchKernelGGL((tl_tg_multi_kernel<VT, XT, SQ, decltype(pt)::value>), dim3(grid), dim3(256), 0, st,
+                         c->groups, c->ngroups, c->items, ni, c->ptrs, (const XT*)x, G, c->dim, parts, c->live,
+                         c->live_g, g_gate, c->tickets, sched, ka, kb);
     });
     if (rt) return rt;
     LAUNCH_CHECK();
@@ -4116,6 +4206,8 @@ int pml_ls_step_grad(const double* x0, const double* d, double t, const double* 
 
 int pml_version() { return 1; }
 void pml_tl_set_deep(int fwd, int t) { g_tl_deep = fwd; g_tl_deep_t = t; }
+// experiment build: schedule of tl_tg_multi_kernel, (0, a, b) static a : b, (1, k, 0) persistent with k group slots
+void pml_tl_set_tg_sched(int sched, int a, int b) { g_tg_sched = sched; g_tg_a = a; g_tg_b = b; }
 
 void pml_set_ls_args(double* z0, double t0, double tpend) { g_ls_z0 = z0; g_ls_t0 = t0; g_ls_tpend = tpend; }
 void pml_set_ls_in(const double* z0_in, const double* zd_in) { g_ls_z0_in = z0_in; g_ls_zd_in = zd_in; }

@@ -59,7 +59,8 @@ class TLTMultiDesc(ctypes.Structure):
     _fields_ = [("items", c_void_p), ("nitems", c_int), ("cbits", c_int), ("ptrs", c_void_p),
                 ("mt_tiles", c_void_p), ("mt_ptr", c_void_p), ("nmt", c_int), ("dim", c_int), ("cu", c_void_p),
                 ("ncu", c_int), ("nparts_total", c_int), ("il", c_int), ("live", c_void_p), ("live_mt", c_void_p),
-                ("groups", c_void_p), ("ngroups", c_int), ("live_g", c_void_p)]
+                ("groups", c_void_p), ("ngroups", c_int), ("live_g", c_void_p),
+                ("tickets", c_void_p)]      # two uint32 unit counters of the persistent tl_tg_multi_kernel
 
 
 class CmpArgs(ctypes.Structure):
@@ -187,6 +188,7 @@ def glm_lib() -> Optional[ctypes.CDLL]:
                                           c_void_p, c_int, c_void_p]
         lib.pml_two_loop_gram_grid.argtypes = [ctypes.c_longlong]
         lib.pml_tl_set_deep.argtypes = [c_int, c_int]
+        lib.pml_tl_set_tg_sched.argtypes = [c_int, c_int, c_int]
         lib.pml_rs_set_variant.argtypes = [c_int]
         lib.pml_rs_set_variant(int(os.environ.get("PML_RS_VARIANT", "5")))
         lib.pml_ls_eval.argtypes = [c_int, c_int, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
@@ -213,7 +215,10 @@ def glm_lib() -> Optional[ctypes.CDLL]:
 # table of the most frequent features; transpose = strided layout. Env overrides for experiments:
 # PML_FWD_STRIDED, PML_T_STRIDED, PML_HOT_N, PML_FWD_GRID.
 KERNEL_CONFIG = {"fwd_strided": 0, "t_strided": 0, "hot_n": 0, "fwd_grid": 1024, "tl_acc64": 1, "tl_waves": 2,
-                 "tl_waves_t": 4, "tl_pipe": 0, "tl_pipe_t": 0, "tl_multi": 1, "tl_deep": 0, "tl_deep_t": 0}
+                 "tl_waves_t": 4, "tl_pipe": 0, "tl_pipe_t": 0, "tl_multi": 1, "tl_deep": 0, "tl_deep_t": 0,
+                 # experiment build only: schedule of the grouped shard-wide transpose (0 static a : b, 1 persistent
+                 # with a = k group slots of 5; b < 0: static in the proportion groups : items); None: the library's
+                 "tl_tg_sched": None, "tl_tg_a": 4, "tl_tg_b": 0}
 
 
 def configure(**kw):
@@ -229,6 +234,8 @@ def configure(**kw):
         lib.pml_tl_config(KERNEL_CONFIG["tl_acc64"], KERNEL_CONFIG["tl_waves"], KERNEL_CONFIG["tl_waves_t"],
                           (KERNEL_CONFIG["tl_pipe"] & 3) | ((KERNEL_CONFIG["tl_pipe_t"] & 3) << 2))
         lib.pml_tl_set_deep(KERNEL_CONFIG["tl_deep"], KERNEL_CONFIG["tl_deep_t"])
+        if KERNEL_CONFIG["tl_tg_sched"] is not None:
+            lib.pml_tl_set_tg_sched(KERNEL_CONFIG["tl_tg_sched"], KERNEL_CONFIG["tl_tg_a"], KERNEL_CONFIG["tl_tg_b"])
     return dict(KERNEL_CONFIG)
 
 

@@ -149,6 +149,7 @@ TALL_COLS = 10           # ints per row of a tall unit table
 # Engaged per SHARD (shard_tgroup): bit-for-bit equal results; on the 125M-row headline 33.38-33.48 vs 34.14-34.18
 # ms/step (three alternated runs each), neutral at 62.5M rows and SLOWER on small shards, whose few groups are long
 # one-wave units that leave CUs idle (16M rows: 5.76 vs 4.88 ms/step, 3M rows: 2.83 vs 1.27); profiles/tl_t_groups.md.
+# Re-measured with the persistent scheduler of tl_tg_multi_kernel: profiles/tl_tg_sched.md (the rule stays).
 TGROUP_DEFAULT = True    # False: only PML_TL_TGROUP=1 / the constructor argument
 TG_MIN_CHUNKS = 96       # full chunks of a shard for the groups to engage on their own (~22K groups at the bench shape)
 TG_BITS = 12             # columns of a tile group (2^12 fp64 sums = 32 KB of LDS per work-group)
@@ -1043,10 +1044,13 @@ class TLTMulti:
         # group rows as the chunks' (TG_COLS ints; tile0 global, the tiles' shard-wide slots, [21] chunk, [22] row
         # base); [23], the group's row in its chunk's table, is for the host emulation
         self.groups = torch.tensor(grp.astype(np.int32), device=dev).reshape(-1, TG_COLS)
+        # the unit counters of the persistent grouped launch (group queue, item queue), zeroed before every launch
+        self.tickets = torch.zeros(2, dtype=torch.int32, device=dev) if self.ngroups else None
         self.desc = TLTMultiDesc(self.items.data_ptr(), n, self.cbits, self.ptrs.data_ptr(),
                                  self.mt_tiles.data_ptr(), self.mt_ptr.data_ptr(), self.nmt, dim,
                                  self.cu.data_ptr(), self.ncu, self.nparts, self.il,
-                                 groups=self.groups.data_ptr() if self.ngroups else None, ngroups=self.ngroups)
+                                 groups=self.groups.data_ptr() if self.ngroups else None, ngroups=self.ngroups,
+                                 tickets=self.tickets.data_ptr() if self.ngroups else None)
 
     @property
     def parts_needed(self) -> int:
